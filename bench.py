@@ -17,7 +17,13 @@ barrier + device synchronize.  Inputs (images, GT) are resident in HBM / host me
 For the inference workloads a step is one batch through net.eval() (BatchNorm folded into the conv epilogues, on-device
 post-process, list[dict] result) and `value` is images / s.
 
-Extra objects:
+A plain run sets up, conditions and warms up, times the K steps and prints the line; the extra objects below are measured only
+with `--full` (they are null otherwise).  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32,
+at most 64 MB in all; arrays too large for that are a fixed, seeded sample of their elements), so that two builds can be compared
+output for output.  With it the conditioning runs a fixed number of steps, so that the last timed step starts from the same
+weights, optimizer state and target stream in every run with the same arguments.
+
+Extra objects (--full):
   roofline     -- the dominant MFMA kernel family BY TIME of the bracketed step, whichever that is (since round 3: the weight-gradient
                   GEMMs, conv_wgrad_kernel; `roofline.kernel` names it, `conv_kernel_groups` has every group).  Every launch of
                   one extra, untimed step is bracketed by HIP events on the launch stream; achieved = sum of ALGORITHMIC fp32
@@ -218,6 +224,31 @@ def cpu_baseline(config_name, H, W, train, batch=1, budget_s=30.0):
             "samples": samples}
 
 
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: `arrays` (name -> tensor or None) as out_dir/<name>.npy, float32, within DUMP_BYTES.  Smallest first, an array is kept
+    whole while an equal share of the budget left holds it; a larger one is written as a sample of its flattened elements (indices drawn by a
+    numpy RandomState seeded with the name's CRC32, sorted): the same elements in every run with the same shapes.  None is an empty array."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: (0 if kv[1] is None else kv[1].numel(), kv[0]))
+    left = DUMP_BYTES // 4 - 64 * len(items)                   # float32 elements (64 per file set aside for the .npy header)
+    for i, (name, t) in enumerate(items):
+        n = 0 if t is None else t.numel()
+        keep = min(n, left // (len(items) - i))
+        if t is None:
+            a = np.zeros(0, np.float32)
+        elif keep == n:
+            a = t.detach().float().cpu().numpy()
+        else:
+            idx = np.sort(np.random.RandomState(zlib.crc32(name.encode())).randint(0, n, keep))
+            a = t.detach().reshape(-1)[torch.from_numpy(idx).to(t.device)].float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32))
+        left -= a.size
+
+
 WORKLOADS = {   # name -> (config, per-GPU batch, H, W, train?, description)
     "c3": ("PlaneRecNet_101_config", 8, 480, 640, True, "train step (fwd + 5-term loss + bwd + grad all-reduce + Adam)"),
     "c1": ("PlaneRecNet_50_config", 1, 480, 640, False, "eval forward + on-device post-process"),
@@ -252,6 +283,10 @@ def main():
                     "this board before the warm-up (ops.autotune_split_policy).  Off by default: the board's clock answers over seconds, blocks of ten "
                     "steps under-estimate the penalty of the broad setting (50.4 vs 50.2 ms in-process where separate runs give 51.4 vs 50.1)")
     ap.add_argument("--no-exchange-probe", action="store_true", help="skip the extra steps that time the gradient-exchange path on a one-rank group")
+    ap.add_argument("--full", action="store_true", help="also measure the extra objects (roofline, cpu_baseline, fp32_only_run, conditioned_run, "
+                    "dcn_offsets_run, host enqueue probe, exchange_probe); a plain run measures the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (float32, "
+                    "<= 64 MB in all, seeded samples of the larger arrays); the conditioning then runs a fixed number of steps")
     ap.add_argument("--graph", action="store_true", help="replay the network's forward / backward as two hipGraphs (measured SLOWER "
                     "than eager launches on ROCm 7.2 in round 1: 144.7 vs 134.3 ms/step -- ~2000 kernel nodes per replay.  Since the per-step operand refresh of the 16-bit-pipe launches "
                     "(ops.split_refresh_all) uploads its item table from pageable memory whenever the set of derived buffers changes -- which a capture's private pool makes happen -- "
@@ -276,7 +311,10 @@ def main():
             port = s_.getsockname()[1]
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-        os.execv(sys.executable, cmd)
+        import subprocess
+        sys.stdout.flush()
+        rc = subprocess.run(cmd).returncode                     # (a child process; this one never touches the GPU)
+        raise SystemExit(rc if rc >= 0 else 128 - rc)
     if world != args.gpus:
         raise SystemExit("bench.py: --gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
     if not torch.cuda.is_available():
@@ -374,6 +412,8 @@ def main():
                 ev.record()
                 ph.setdefault("_gap_b", []).append(ev)
             out = run_net(images)
+            if args.dump_outputs:                                # (values only, as for the losses below)
+                pipe["out"] = [[t.detach() for t in o] if isinstance(o, (list, tuple)) else o.detach() for o in out]
             t3 = time.perf_counter()
             losses = crit(net, *out, inst, depths, targets=targets)
             loss = sum(losses.values()).sum()
@@ -469,11 +509,12 @@ def main():
             el = float(t.item())
         return el, out
 
-    def condition(max_steps=40, tol=0.01):
+    def condition(max_steps=40, tol=0.01, fixed=False):
         """Untimed conditioning BEFORE the contract's warm-up: blocks of BLOCK steps until two consecutive blocks agree within `tol` (at most max_steps).
         A fresh lease pays its first-use costs here -- code-object loads of every kernel, the caching allocator's growth to the step's working set,
         the per-shape plans / descriptors / block states of the host layer, the board's clock ramp -- instead of inside the first timed steps
-        (round 5: the driver's 5 + 20 steps read 45.7 ms where later legs of the same process read 42.2-43.4)."""
+        (round 5: the driver's 5 + 20 steps read 45.7 ms where later legs of the same process read 42.2-43.4).
+        fixed: always max_steps (a training step's result depends on how many steps came before it: --dump-outputs)."""
         ms, used = [], 0
         while used < max_steps:
             fence()
@@ -488,7 +529,7 @@ def main():
                 el = float(t.item())
             ms.append(round(1e3 * el / BLOCK, 3))
             used += BLOCK
-            if len(ms) >= 2 and abs(ms[-1] - ms[-2]) <= tol * ms[-2]:
+            if not fixed and len(ms) >= 2 and abs(ms[-1] - ms[-2]) <= tol * ms[-2]:
                 break
         return ms
 
@@ -505,14 +546,29 @@ def main():
         for _ in range(3):
             step()
         tune = ops.autotune_split_policy(step, "train" if train else "eval", reduce_max=rmax)
-    conditioning = condition() if not os.environ.get("PRN_BENCH_NO_CONDITIONING") else []
+    conditioning = condition(fixed=bool(args.dump_outputs)) if not os.environ.get("PRN_BENCH_NO_CONDITIONING") else []
     n_host0 = len(ph.get("host_ms_per_step", []))
     cpu0 = time.process_time()
     elapsed, last = timed(args.warmup, args.steps, tag="headline")
+    if args.dump_outputs and rank == 0:                      # (before any other leg: those run more steps, and dcn_offsets_run changes the weights)
+        if train:                                            # the losses the step returned, the forward's outputs, the parameters after Adam and their gradients
+            arrays = {"loss_" + k: v for k, v in last.items()}
+            mask, cate, kern, depth = pipe["out"]
+            arrays.update({"mask_pred": mask, "depth_pred": depth})
+            arrays.update({"cate_pred_%d" % i: t for i, t in enumerate(cate)})
+            arrays.update({"kernel_pred_%d" % i: t for i, t in enumerate(kern)})
+            with torch.no_grad():
+                ps = list(net.parameters())
+                arrays["parameters"] = torch.cat([p.detach().reshape(-1) for p in ps])
+                arrays["gradients"] = torch.cat([(torch.zeros_like(p) if p.grad is None else p.grad.detach()).reshape(-1) for p in ps])
+        else:                                                # the list[dict] of the post-process, image by image
+            arrays = {"img%d_%s" % (b, k): v for b, r in enumerate(last) for k, v in r.items()}
+        dump_outputs(args.dump_outputs, arrays)
+        del arrays
     # host side of the timed steps on this rank: wall time the trainer thread needs to enqueue a step, and CPU time of the whole
     # process (trainer + autograd + receiver threads; the target workers are separate processes) -- at N ranks per host these add up
     host = None
-    if train:
+    if train and args.full:
         hs = ph.get("host_ms_per_step", [])[n_host0 + args.warmup:]
         cpu_free = 1e3 * (time.process_time() - cpu0) / max(args.steps + args.warmup, 1)
         # What the trainer needs to ENQUEUE a step: each probe step is issued while the stream is parked behind a spin kernel, so no launch waits for queue
@@ -546,7 +602,7 @@ def main():
     # cost of the gradient-exchange path itself (hooks, bucket pack, one-rank RCCL all-reduce, `.grad` re-pointing) before any wire
     # time: the same step with the exchange forced on a one-rank group (N = 1 only; with N > 1 it is always on)
     exch = None
-    if train and world == 1 and rank == 0 and not graphed and not args.no_exchange_probe and not exchange.active:
+    if args.full and train and world == 1 and rank == 0 and not graphed and not args.no_exchange_probe and not exchange.active:
         try:
             if not dist.is_initialized():
                 os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -601,7 +657,7 @@ def main():
     roof, kernels = None, None
     # (EVERY rank runs this leg: its steps contain the gradient exchange and `timed` ends in a barrier and a reduction -- rank 0 alone would issue
     # collectives nobody answers.  Only rank 0's brackets are reported.)
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         if graphed:
             raise SystemExit("bench.py: the roofline leg needs eagerly issued launches; combine --graph with --no-roofline")
         branch_streams, ops.BRANCH_STREAMS = ops.BRANCH_STREAMS, False      # one stream: an event pair then times one launch, not its neighbours
@@ -735,7 +791,7 @@ def main():
 
     # the same step with every contraction on the fp32 MFMA kernels (same weights, same process, after the headline timing)
     fp32_run = None
-    if not graphed and ops.split_mode() != 0 and not os.environ.get("PRN_BENCH_NO_FP32_RUN"):
+    if args.full and not graphed and ops.split_mode() != 0 and not os.environ.get("PRN_BENCH_NO_FP32_RUN"):
         old_pol = ops.set_split_gemm(mode=0)
         n2 = max(args.steps // 2, 5)
         el2, _ = timed(3, n2)
@@ -747,7 +803,7 @@ def main():
     # inference workloads: the timed post-process at the init state sees (almost) no candidates.  Shift the category bias until every image
     # keeps >= 5 detections and time the same batch again (the product's own forward picks the shift: no oracle on this path).
     cond_run = None
-    if not train and not os.environ.get("PRN_BENCH_NO_CONDITIONED_RUN"):       # (every rank: `timed` synchronises the ranks; the shift is agreed by a MIN over ranks)
+    if args.full and not train and not os.environ.get("PRN_BENCH_NO_CONDITIONED_RUN"):       # (every rank: `timed` synchronises the ranks; the shift is agreed by a MIN over ranks)
         bias = net.inst_head.cate_pred.bias
         b0 = bias.detach().clone()
         for shift in (0.5, 1.0, 1.5, 2.0, 2.5, 3.0, 3.5, 4.0):
@@ -769,7 +825,7 @@ def main():
 
     # the same step with non-trivial deformable offsets (after the headline timing; the weights change)
     dcn_run = None
-    if train and args.dcn_offsets > 0 and not graphed:
+    if args.full and train and args.dcn_offsets > 0 and not graphed:
         set_dcn_offsets(args.dcn_offsets)
         n2 = max(args.steps // 2, 3)
         el2, l2 = timed(2, n2)
@@ -777,7 +833,7 @@ def main():
                    "losses_finite": all(bool(torch.isfinite(v).all()) for v in l2.values())}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.config, args.height, args.width, train, batch=args.batch)
 
     # The JSON line must be the LAST thing on the job's stdout: RCCL writes its version banner through C stdio, which sits in the

@@ -60,12 +60,12 @@ def _two_rank_env():
 def test_bench_self_launches_two_ranks(tmp_path):
     """`python bench.py --gpus 2` with no launcher around it (the driver's SCALE command): bench.py re-executes itself under
     torch.distributed.run, one process per rank, and rank 0 prints the one JSON line with the whole-job throughput.  With EVERY leg of the
-    default command on (roofline brackets, fp32-only re-run, DCN-offset re-run): until the end of round 4 the roofline leg ran on rank 0 only,
+    --full command on (roofline brackets, fp32-only re-run, DCN-offset re-run): until the end of round 4 the roofline leg ran on rank 0 only,
     and its steps' collectives and `timed`'s barrier had no partner -- `bench.py --gpus N` hung for N > 1 unless --no-roofline was passed,
     which is what this test used to pass."""
     import json
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--config",
-                        "PlaneRecNet_50_config", "--batch", "2"], cwd=str(tmp_path), capture_output=True,
+                        "PlaneRecNet_50_config", "--batch", "2", "--full"], cwd=str(tmp_path), capture_output=True,
                        text=True, timeout=900, env=_two_rank_env())
     assert r.returncode == 0, r.stdout[-2000:] + "\n" + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -79,7 +79,7 @@ def test_bench_self_launches_two_ranks(tmp_path):
 def test_bench_inference_two_ranks(tmp_path):
     """An inference workload under two ranks: the conditioned re-run (rank 0 only until round 4) synchronises the ranks as well."""
     import json
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "c1", "--steps", "3", "--warmup", "2"], cwd=str(tmp_path),
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "c1", "--steps", "3", "--warmup", "2", "--full"], cwd=str(tmp_path),
                        capture_output=True, text=True, timeout=900, env=_two_rank_env())
     assert r.returncode == 0, r.stdout[-2000:] + "\n" + r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
@@ -90,7 +90,7 @@ def test_bench_inference_two_ranks(tmp_path):
 def test_bench_inference_workloads(tmp_path, workload, batch, hw):
     """BASELINE.json configs 1 / 2 / 5 as bench lines: eval forward + on-device post-process, same JSON schema as the headline."""
     import json
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--steps", "3", "--warmup", "2", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--steps", "3", "--warmup", "2", "--full", "--no-cpu-baseline"],
                        cwd=str(tmp_path), capture_output=True, text=True, timeout=900, env=dict(os.environ, PYTHONPATH=ROOT))
     assert r.returncode == 0, r.stdout[-2000:] + "\n" + r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])

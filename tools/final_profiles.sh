@@ -5,8 +5,8 @@ TAG=${1:-rXX}
 O=$R/gpurun_out/final
 mkdir -p $O
 cd $R
-python bench.py 2>$O/${TAG}_bench_c3.stderr | grep "^{" | tail -1 > $O/${TAG}_bench_c3.json
-for w in c1 c2 c5; do python bench.py --workload $w 2>/dev/null | grep "^{" | tail -1 > $O/${TAG}_bench_$w.json; done
+python bench.py --full 2>$O/${TAG}_bench_c3.stderr | grep "^{" | tail -1 > $O/${TAG}_bench_c3.json
+for w in c1 c2 c5; do python bench.py --full --workload $w 2>/dev/null | grep "^{" | tail -1 > $O/${TAG}_bench_$w.json; done
 bash tools/rocprof_stats.sh $TAG > $O/${TAG}_kernel_stats_summary.txt 2>&1
 cp gpurun_out/prof/${TAG}_kernel_stats_serial.csv $O/${TAG}_kernel_stats_serial_sync_wgrad.csv
 cp gpurun_out/prof/${TAG}_kernel_stats_default.csv $O/${TAG}_kernel_stats_default_overlapped.csv
