@@ -718,6 +718,32 @@ int prn_adam_step_masked(const int* chunks, int nchunks, int ntensors, float* co
                          const float* lr, float* step, const float* found_inf, const float* grad_scale, double beta1, double beta2, float eps,
                          const float* present, const int* present_idx, void* stream);
 
+/* ---- plane parameters of detected instances and the planar depth map (csrc/prn_planes.hip) -------------------------------------
+ * replaces the per-instance loop of the reference's iBims-1 "plane depth" exporter (simple_inference.py:240-324: boolean indexing,
+ * PCA_svd of models/functions/funcs.py:287-291, torch.where per instance).  A ragged batch of B images, N_b instances each:
+ *   depth      [B][H][W] fp32 (the predicted depth; never written)
+ *   masks_dev  DEVICE array [B] of pointers to each image's byte masks [N_b][H][W] (non-zero = set; N_b = 0: never read)
+ *   first_dev  DEVICE array [B+1] int: first_dev[b] = N_0 + ... + N_{b-1}, first_dev[B] = Ntot (global instance index = first + local)
+ *   k_dev      DEVICE array [B][3][3] fp64: the intrinsics K of each image (row-major: fx = K[0][0], cx = K[0][2], fy = K[1][1], cy = K[1][2])
+ * prn_planes_fit: for every instance, the pixels (v, u) of its mask back-projected in fp64 (X = (u - cx) Z / fx, Y = (v - cy) Z / fy, Z;
+ * integer pixel indices), their centroid c and the unit eigenvector n of the smallest eigenvalue of the centred scatter
+ * sum (p - c)(p - c)^T (the reference's third singular vector) ->
+ *   planes [Ntot][4] fp64 = (nx, ny, nz, d), n . X = d, sign of n chosen so that d >= 0; NaN for an invalid instance
+ *   centroid [Ntot][3] fp64 (NaN for an empty mask), valid [Ntot] uint8, count [Ntot] int64 (pixels of the mask)
+ * An instance is invalid with fewer than 3 pixels or a degenerate scatter (middle eigenvalue <= 1e-12 x the largest: collinear points).
+ * prn_planes_render (after prn_planes_fit on the same workspace, which holds the per-pixel owner map): out[b] = depth[b] with every pixel
+ * a valid instance covers replaced by the plane depth of the HIGHEST-index valid covering instance, d / (n . K^-1 [u, v, 1]^T) (fp64,
+ * stored fp32) -- the reference's `for i: depth = where(mask_i, plane_depth_i, depth)`; has_range != 0: values <= lo or >= hi (and NaN)
+ * become NaN.  out must not alias depth.
+ * ws: prn_planes_ws_bytes(B, Ntot, H, W) bytes (-1: invalid sizes), 16-byte aligned; per (instance, 1024-pixel tile) partial moments and
+ * the owner map.  Three launches in all, no host synchronisation; results are bit-identical run to run and between a batched call and
+ * per-image calls. */
+int64_t prn_planes_ws_bytes(int B, int Ntot, int H, int W);
+int prn_planes_fit(const float* depth, const unsigned char* const* masks_dev, const int* first_dev, const double* k_dev, int B, int Ntot, int H, int W,
+                   double* planes, double* centroid, unsigned char* valid, int64_t* count, void* ws, void* stream);
+int prn_planes_render(const float* depth, const unsigned char* const* masks_dev, const int* first_dev, const double* k_dev, const double* planes,
+                      const unsigned char* valid, int B, int Ntot, int H, int W, int has_range, float lo, float hi, float* out, const void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -203,6 +203,9 @@ SIGNATURES = {
     "prn_bottleneck_plan_info": (c_int, [P, ctypes.POINTER(c_i64), c_int]),
     "prn_bottleneck_train_fwd": (c_int, [P, ctypes.POINTER(BottleneckParams), P, P, P, P, P]),
     "prn_bottleneck_train_bwd": (c_int, [P, ctypes.POINTER(BottleneckParams), P, P, P, P, c_int, P, P, P, P, P]),
+    "prn_planes_ws_bytes": (c_i64, [c_int] * 4),
+    "prn_planes_fit": (c_int, [P] * 4 + [c_int] * 4 + [P] * 6),
+    "prn_planes_render": (c_int, [P] * 6 + [c_int] * 5 + [c_float, c_float, P, P, P]),
 }
 
 

@@ -1,0 +1,128 @@
+"""Plane parameters of detected instances and the planar depth map (include/prn.h: prn_planes_*).
+
+The reference derives them only in its iBims-1 "plane depth" exporter (simple_inference.py:240-324): per instance, the depth
+under the mask back-projected with the intrinsics K, the plane through the centroid normal to the smallest principal axis
+(PCA_svd, models/functions/funcs.py:287-291), and the depth inside the mask replaced by that plane's ray-intersection depth,
+the highest-index instance winning where masks overlap.  Here a whole ragged batch is three HIP launches and no host
+synchronisation (sizes come from tensor shapes, which the host knows).
+
+Deviations where the reference crashes or returns an arbitrary plane: an instance with fewer than 3 pixels or collinear points
+(a degenerate scatter) is INVALID -- NaN plane, no part in the composition (its pixels take the next valid covering instance
+below it, or keep the predicted depth).  The reference raises on a 1-pixel mask (`squeeze` turns the [1,3] point set into a
+vector) and returns an arbitrary plane for 2 pixels.
+"""
+import ctypes
+
+import torch
+
+from ._lib import check, lib
+
+__all__ = ["fit_planes", "planar_depth"]
+
+
+def _p(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _upload(values, dtype, device):
+    """host values -> device tensor through page-locked memory (an asynchronous copy: no host synchronisation)"""
+    return torch.tensor(values, dtype=dtype).pin_memory().to(device, non_blocking=True)
+
+
+def _intrinsics(k_matrix, B, device):
+    """K as [3,3] or [B,3,3] (tensor anywhere or array) -> [B,9] fp64 on the device"""
+    k = torch.as_tensor(k_matrix)
+    if k.shape not in ((3, 3), (B, 3, 3)):
+        raise RuntimeError("k_matrix must be [3,3] or [B,3,3] (B=%d), got %s" % (B, tuple(k.shape)))
+    if k.is_cuda:
+        k = k.to(device=device, dtype=torch.float64)
+    else:
+        k = k.to(torch.float64).contiguous().pin_memory().to(device, non_blocking=True)
+    return k.expand(B, 3, 3).reshape(B, 9).contiguous()
+
+
+class _Fit:
+    """one prn_planes_fit call: its device tables, outputs and workspace (the render launch reads the same workspace)"""
+
+    def __init__(self, depth, masks, k_matrix):
+        if not (torch.is_tensor(depth) and depth.is_cuda and depth.dtype == torch.float32 and depth.dim() == 4 and depth.shape[1] == 1):
+            got = "%s %s %s" % (depth.device, depth.dtype, tuple(depth.shape)) if torch.is_tensor(depth) else type(depth).__name__
+            raise RuntimeError("depth must be a [B,1,H,W] fp32 device tensor, got %s" % got)
+        B, _, H, W = depth.shape
+        dev = depth.device
+        if len(masks) != B:
+            raise RuntimeError("masks: one [N,H,W] tensor per image expected (%d images, %d mask tensors)" % (B, len(masks)))
+        ms = []
+        for b, m in enumerate(masks):
+            if m is None:
+                m = torch.zeros(0, H, W, dtype=torch.uint8, device=dev)
+            if not (m.device == dev and m.dtype in (torch.bool, torch.uint8) and m.dim() == 3 and tuple(m.shape[1:]) == (H, W)):
+                raise RuntimeError("masks[%d] must be a bool / uint8 [N,%d,%d] tensor on %s, got %s %s %s" % (b, H, W, dev, m.device, m.dtype, tuple(m.shape)))
+            m = m.contiguous()
+            ms.append(m.view(torch.uint8) if m.dtype == torch.bool else m)
+        self.sizes = [int(m.shape[0]) for m in ms]
+        first = [0]
+        for n in self.sizes:
+            first.append(first[-1] + n)
+        self.B, self.H, self.W, self.Ntot = B, H, W, first[-1]
+        self.depth = depth.contiguous()
+        self.masks = ms                                          # (kept alive with the pointer table)
+        self.ptrs = _upload([m.data_ptr() for m in ms], torch.int64, dev)
+        self.first = _upload(first, torch.int32, dev)
+        self.k = _intrinsics(k_matrix, B, dev)
+        nbytes = lib.prn_planes_ws_bytes(B, self.Ntot, H, W)
+        if nbytes < 0:
+            raise RuntimeError("prn_planes_ws_bytes: invalid sizes B=%d Ntot=%d H=%d W=%d" % (B, self.Ntot, H, W))
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.planes = torch.empty(self.Ntot, 4, dtype=torch.float64, device=dev)
+        self.centroid = torch.empty(self.Ntot, 3, dtype=torch.float64, device=dev)
+        self.valid = torch.empty(self.Ntot, dtype=torch.bool, device=dev)
+        self.count = torch.empty(self.Ntot, dtype=torch.int64, device=dev)
+        self.stream = ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index))
+        check(lib.prn_planes_fit(_p(self.depth), _p(self.ptrs), _p(self.first), _p(self.k), B, self.Ntot, H, W, _p(self.planes), _p(self.centroid),
+                                 _p(self.valid), _p(self.count), _p(self.ws), self.stream), "prn_planes_fit")
+
+    def render(self, depth_range=None):
+        out = torch.empty_like(self.depth)
+        lo, hi = (0.0, 0.0) if depth_range is None else (float(depth_range[0]), float(depth_range[1]))
+        check(lib.prn_planes_render(_p(self.depth), _p(self.ptrs), _p(self.first), _p(self.k), _p(self.planes), _p(self.valid), self.B, self.Ntot,
+                                    self.H, self.W, int(depth_range is not None), lo, hi, _p(out), _p(self.ws), self.stream), "prn_planes_render")
+        return out
+
+    def split(self, t):
+        return list(torch.split(t, self.sizes))
+
+
+@torch.no_grad()
+def fit_planes(depth, masks, k_matrix):
+    """Fits one plane per instance mask.
+
+    depth    [B,1,H,W] fp32 device tensor (the predicted depth)
+    masks    list of B [N_b,H,W] bool / uint8 device tensors (N_b may be 0; None = no instances)
+    k_matrix intrinsics K, [3,3] or [B,3,3] (for an iBims-1 file: calib.T)
+    -> (planes, valid, count): lists of B per-image tensors -- planes [N_b,4] fp64 (nx, ny, nz, d) in camera coordinates with
+       n . X = d and d >= 0 (NaN rows for invalid instances), valid [N_b] bool, count [N_b] int64 (pixels of each mask)."""
+    f = _Fit(depth, masks, k_matrix)
+    return f.split(f.planes), f.split(f.valid), f.split(f.count)
+
+
+@torch.no_grad()
+def planar_depth(results, k_matrix, depth_range=None):
+    """The planar depth of PlaneRecNet's eval-mode output (the list of per-image dicts): for every image a NEW dict with the
+    input's entries plus
+       pred_planes      [N,4] fp64 (see fit_planes; [0,4] when the image has no detections)
+       pred_plane_valid [N] bool
+       pred_plane_depth [1,1,H,W] fp32: pred_depth with every pixel a valid instance covers replaced by the plane depth of the
+                        highest-index valid covering instance (the lowest-scored one: detections come in descending score order)
+    depth_range = (lo, hi): values <= lo or >= hi become NaN afterwards (the iBims-1 exporter uses (0, 10)).
+    The input dicts and their tensors are not modified."""
+    depth = torch.cat([r["pred_depth"].reshape(1, 1, *r["pred_depth"].shape[-2:]) for r in results]).float()
+    f = _Fit(depth, [r.get("pred_masks") for r in results], k_matrix)
+    out = f.render(depth_range)
+    planes, valid = f.split(f.planes), f.split(f.valid)
+    new = []
+    for b, r in enumerate(results):
+        d = dict(r)
+        d["pred_planes"], d["pred_plane_valid"], d["pred_plane_depth"] = planes[b], valid[b], out[b:b + 1]
+        new.append(d)
+    return new

@@ -5,8 +5,16 @@
 The tensor path is the reference's: read BGR image -> resize to calc_size_preserve_ar(W, H, cfg.max_size) (cv2.INTER_LINEAR
 arithmetic, no antialiasing) -> zero-pad to a multiple of 32 -> FastBaseTransform -> PlaneRecNet (eval) -> list[dict]; the
 three staging steps run as one HIP launch on the uploaded uint8 frame.  The device comes from `cfg.device`.
-Image file I/O and the overlay drawing use Pillow + numpy (OpenCV is not a dependency of this build); the iBims-1 `.mat`
-exporters of the reference are visual / evaluation tooling outside the hot path and are not provided.
+Image file I/O and the overlay drawing use Pillow + numpy (OpenCV is not a dependency of this build).
+
+iBims-1 exporters (`--ibims1 in:out`, `--ibims1_pd in:out`, reference simple_inference.py:202-324): every `.mat` file of `in`
+(sorted; `data['rgb'][0][0]` uint8 [H,W,3], `data['calib'][0][0]` 3x3 with K = calib.T) goes through the network at its native
+size (padded to a multiple of 32, outputs cropped back) and gives `out/<name>_results.mat` = {'pred_depths': float32 [H,W]} plus a
+viridis preview `out/<name>_results.png`.  --ibims1 writes the predicted depth; --ibims1_pd the planar depth (planerecnet_amd.planes:
+every detected plane's depth replaces the prediction under its mask), values <= 0 or >= 10 set to NaN.  Quirks kept: the `.mat`'s
+rgb array enters FastBaseTransform as if it were BGR, as in the reference.  Deviation: the preview's 1 / 99 % limits come from
+np.nanpercentile (the reference's np.percentile turns a NaN-holding map into a meaningless image).  scipy is needed for these
+two flags only.
 """
 import argparse
 import os
@@ -28,8 +36,9 @@ def parse_args(argv=None):
     p.add_argument("--image", default=None, type=str, help="path or input:output")
     p.add_argument("--images", default=None, type=str, help="input_folder:output_folder")
     p.add_argument("--max_img", default=0, type=int)
-    p.add_argument("--ibims1", default=None, type=str, help="not provided by this build")
-    p.add_argument("--ibims1_pd", default=None, type=str, help="not provided by this build")
+    p.add_argument("--ibims1", default=None, type=str, help="in_folder:out_folder -- predicted depth of every iBims-1 .mat file -> <name>_results.mat/png")
+    p.add_argument("--ibims1_pd", default=None, type=str,
+                   help="in_folder:out_folder -- planar depth (each detected plane's depth under its mask, values outside (0, 10) NaN) -> <name>_results.mat/png")
     p.add_argument("--no_mask", action="store_true")
     p.add_argument("--no_box", action="store_true")
     p.add_argument("--no_text", action="store_true")
@@ -83,6 +92,14 @@ def display_on_frame(result, frame, mask_alpha=0.5, no_mask=False, no_box=False,
     return np.asarray(pil)[:, :, ::-1], depth
 
 
+def _viridis(depth, vmin, vmax):
+    """depth clipped to [vmin, vmax], stretched to 0..255 and mapped through a 5-stop viridis ramp -> uint8 [H,W,3] RGB"""
+    d = depth.clip(min=vmin, max=vmax)
+    lo, hi = (np.nanmin(d), np.nanmax(d)) if np.isfinite(d).any() else (0.0, 0.0)
+    d = np.nan_to_num((d - lo) / max(hi - lo, 1e-12) * 255, nan=0.0).astype(np.uint8)
+    return np.stack([np.interp(d, [0, 64, 128, 192, 255], c) for c in ([68, 59, 33, 94, 253], [1, 82, 145, 201, 231], [84, 139, 140, 98, 37])], -1)
+
+
 @torch.no_grad()
 def inference_image(net, path, save_path=None, depth_mode="colored"):
     frame_np = _imread_bgr(path)
@@ -101,10 +118,7 @@ def inference_image(net, path, save_path=None, depth_mode="colored"):
     _imwrite_bgr(save_path, blended)
     if depth_mode == "colored":
         vmin, vmax = np.percentile(depth, 1), np.percentile(depth, 99)
-        d = depth.clip(min=vmin, max=vmax)
-        d = ((d - d.min()) / max(d.max() - d.min(), 1e-12) * 255).astype(np.uint8)
-        viridis = np.stack([np.interp(d, [0, 64, 128, 192, 255], c) for c in ([68, 59, 33, 94, 253], [1, 82, 145, 201, 231], [84, 139, 140, 98, 37])], -1)
-        _imwrite_bgr(depth_path, viridis[:, :, ::-1])
+        _imwrite_bgr(depth_path, _viridis(depth, vmin, vmax)[:, :, ::-1])
     else:
         _imwrite_bgr(depth_path, (depth * args.depth_shift).astype(np.uint16))
     return results
@@ -117,6 +131,81 @@ def inference_images(net, in_folder, out_folder, max_img=0, depth_mode="colored"
         inference_image(net, str(p), os.path.join(out_folder, p.name), depth_mode=depth_mode)
         print("Inference images: " + p.name, end="\r")
     print("\nDone.")
+
+
+def _scipy_io():
+    try:
+        import scipy.io
+    except ImportError:
+        raise SystemExit("--ibims1 / --ibims1_pd read and write MATLAB files and need scipy (scipy.io), which is not installed.")
+    return scipy.io
+
+
+def read_ibims1_mat(path):
+    """an iBims-1 .mat file -> (rgb uint8 [H,W,3], K float64 [3,3]); the file stores the intrinsics transposed (K = calib.T)"""
+    data = _scipy_io().loadmat(path)["data"]
+    rgb = np.ascontiguousarray(data["rgb"][0][0], dtype=np.uint8)
+    return rgb, np.asarray(data["calib"][0][0], dtype=np.float64).T.copy()
+
+
+def ibims1_inputs(in_folder):
+    """the .mat files of in_folder, sorted, as (name, path)"""
+    return [(p.stem, str(p)) for p in sorted(Path(in_folder).glob("*")) if p.suffix == ".mat"]
+
+
+def ibims1_outputs(out_folder, name):
+    """(<name>_results.mat, <name>_results.png) in out_folder"""
+    base = os.path.join(out_folder, name + "_results")
+    return base + ".mat", base + ".png"
+
+
+@torch.no_grad()
+def ibims1_results(net, rgb):
+    """one iBims-1 frame through the network at native size: the rgb array enters as if it were BGR (the reference's quirk), the
+    input is zero-padded to a multiple of 32 and the outputs are cropped back -> the eval-mode result dict of the frame"""
+    H, W, _ = rgb.shape
+    staged = torch.from_numpy(rgb)
+    if torch.cuda.is_available():
+        staged = staged.pin_memory()
+    batch, _ = frame_to_input(staged.to(cfg.device, non_blocking=True), (W, H), want_frame=False)
+    r = dict(net(batch)[0])
+    r["pred_depth"] = r["pred_depth"][..., :H, :W]
+    if r["pred_masks"] is not None:
+        r["pred_masks"] = r["pred_masks"][:, :H, :W]
+    return r
+
+
+def _ibims1_export(net, in_folder, out_folder, planar):
+    sio = _scipy_io()
+    os.makedirs(out_folder, exist_ok=True)
+    for name, path in ibims1_inputs(in_folder):
+        rgb, k_matrix = read_ibims1_mat(path)
+        r = ibims1_results(net, rgb)
+        if planar:
+            from planerecnet_amd.planes import planar_depth
+            depth = planar_depth([r], k_matrix, depth_range=(0.0, 10.0))[0]["pred_plane_depth"]
+        else:
+            depth = r["pred_depth"]
+        depth = depth.squeeze().float().cpu().numpy()
+        out, preview = ibims1_outputs(out_folder, name)
+        sio.savemat(out, {"pred_depths": depth})
+        if np.isfinite(depth).any():
+            vmin, vmax = np.nanpercentile(depth, 1), np.nanpercentile(depth, 99)
+        else:
+            vmin = vmax = 0.0
+        _imwrite_bgr(preview, _viridis(depth, vmin, vmax)[:, :, ::-1])
+        print(os.path.basename(path) + " -> " + os.path.basename(out), end="\r")
+    print("\nDone.")
+
+
+def ibims1(net, in_folder, out_folder):
+    """--ibims1: the predicted depth of every iBims-1 .mat file (reference simple_inference.py:202-236)"""
+    _ibims1_export(net, in_folder, out_folder, planar=False)
+
+
+def ibims1_pd(net, in_folder, out_folder):
+    """--ibims1_pd: the planar depth, values <= 0 or >= 10 NaN (reference simple_inference.py:240-324)"""
+    _ibims1_export(net, in_folder, out_folder, planar=True)
 
 
 def main(argv=None):
@@ -143,8 +232,12 @@ def main(argv=None):
         print(cfg.backbone.name)
     net.train(mode=False)
     net = net.to(cfg.device)
-    if args.ibims1 is not None or args.ibims1_pd is not None:
-        raise SystemExit("iBims-1 exporters are not part of this build (evaluation tooling outside the hot path).")
+    if args.ibims1 is not None:
+        inp, out = args.ibims1.split(":")
+        ibims1(net, inp, out)
+    if args.ibims1_pd is not None:
+        inp, out = args.ibims1_pd.split(":")
+        ibims1_pd(net, inp, out)
     if args.image is not None:
         inp, out = args.image.split(":") if ":" in args.image else (args.image, None)
         print("Inference image: {}".format(inp))
