@@ -744,6 +744,41 @@ int prn_planes_fit(const float* depth, const unsigned char* const* masks_dev, co
 int prn_planes_render(const float* depth, const unsigned char* const* masks_dev, const int* first_dev, const double* k_dev, const double* planes,
                       const unsigned char* valid, int B, int Ntot, int H, int W, int has_range, float lo, float hi, float* out, const void* ws, void* stream);
 
+/* ---- the inference overlay and the depth picture (csrc/prn_render.hip) ---------------------------------------------------------
+ * What simple_inference.py drew on the host (display_on_frame, _viridis: N full-frame float passes per image), as device launches.
+ * Overlay, ONE launch:
+ *   frame  [H][W][3] fp32 BGR (what the frame staging returns; never written)      masks  [N][H][W] bytes, non-zero = set
+ *   colors [N][3] uint8 BGR, boxes [N][4] int32 (x0, y0, x1, y1; may lie off the image), out [H][W][3] uint8 BGR
+ *   layers: PRN_RENDER_MASKS | PRN_RENDER_CONTOURS | PRN_RENDER_BOXES.  Per pixel, in this order:
+ *     masks     for i = N-1 down to 0, where masks[i] is set: v = fl(fl(v * one_minus_alpha) + fl(colors[i] * alpha)) per channel (fp32, two
+ *               rounded multiplies and one rounded add, never fused); then v truncated toward zero (saturated to [0, 255], NaN -> 0)
+ *     contours  a pixel of masks[i] any of whose four neighbours is outside masks[i] or outside the image becomes (255, 255, 255)
+ *     boxes     for i = 0 .. N-1, later boxes win: pixel (x, y) takes colors[i] if (x in {x0, x1} and y0 <= y <= y1) or
+ *               (y in {y0, y1} and x0 <= x <= x1).  A box with x1 < x0 or y1 < y0 is the caller's to refuse.
+ *   Pointers of a layer that is off (or N = 0) may be NULL.  Every mask byte is read once (with contours: plus a one-pixel halo per
+ *   128 x 8 tile, through LDS).  W % 4 == 0 with a 16-byte aligned frame and 4-byte aligned masks / out takes the wide loads and stores;
+ *   anything else a per-pixel path that writes the same bytes.
+ * Depth limits: prn_render_depth_limits selects, over the non-NaN values of depth [n] and WITHOUT a sort (radix select on the order-preserving
+ *   integer key of the fp32 pattern, integer histograms only: deterministic), the order statistics next to the virtual indices
+ *   (cnt - 1) * q_lo and (cnt - 1) * q_hi (fp64, cnt = the number of non-NaN values, known on the device only; q as fractions in [0, 1]) ->
+ *   limits [8] fp32 = { vmin, vmax, lo_a, lo_b, hi_a, hi_b, min, max }: vmin = fl32(a + (b - a) * g) in fp64 from the two neighbours a <= b
+ *   of the lower index and its fraction g, vmax likewise; the neighbours themselves, exact; the non-NaN minimum and maximum.  Nothing but
+ *   NaN: all eight are 0.  ws: prn_render_limits_ws_bytes() bytes, 16-byte aligned (cleared by the call).  Five launches.
+ * prn_render_depth_colors: level = uint8(trunc(fl(fl(fl(clip(d, vmin, vmax) - lo) / den) * 255))), NaN -> level 0; lo / hi = min / max clipped to
+ *   [vmin, vmax] (the extremes of the clipped map), den = hi - lo, or 1e-12f where 1e-12f is greater (a constant map is all level 0); fp32 with
+ *   a correctly rounded division; out [n][3] = lut [256][3] at the level (the channel order is the table's).  limits: the device array above.
+ * prn_render_depth_gray: out [n] uint16 = trunc(fl(d * shift)) saturated to [0, 65535], NaN -> 0.
+ * No allocation and no synchronisation inside; n < 2^31. */
+#define PRN_RENDER_MASKS 1
+#define PRN_RENDER_CONTOURS 2
+#define PRN_RENDER_BOXES 4
+int prn_render_overlay(const float* frame, const unsigned char* masks, const unsigned char* colors, const int* boxes, int N, int H, int W, float alpha,
+                       float one_minus_alpha, int layers, unsigned char* out, void* stream);
+int64_t prn_render_limits_ws_bytes(void);
+int prn_render_depth_limits(const float* depth, int64_t n, double q_lo, double q_hi, float* limits, void* ws, void* stream);
+int prn_render_depth_colors(const float* depth, int64_t n, const float* limits, const unsigned char* lut, unsigned char* out, void* stream);
+int prn_render_depth_gray(const float* depth, int64_t n, float shift, unsigned short* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,10 @@
 The tensor path is the reference's: read BGR image -> resize to calc_size_preserve_ar(W, H, cfg.max_size) (cv2.INTER_LINEAR
 arithmetic, no antialiasing) -> zero-pad to a multiple of 32 -> FastBaseTransform -> PlaneRecNet (eval) -> list[dict]; the
 three staging steps run as one HIP launch on the uploaded uint8 frame.  The device comes from `cfg.device`.
-Image file I/O and the overlay drawing use Pillow + numpy (OpenCV is not a dependency of this build).
+Image file I/O and the overlay drawing use Pillow + numpy (OpenCV is not a dependency of this build).  `--render device` (not in the
+reference) draws masks, boxes and the depth picture on the GPU instead (planerecnet_amd.render: the same bytes, one uint8 image each
+downloaded, score texts added by Pillow afterwards); `--contours` adds white mask outlines there.  The default, `--render host`, is
+unchanged.
 
 iBims-1 exporters (`--ibims1 in:out`, `--ibims1_pd in:out`, reference simple_inference.py:202-324): every `.mat` file of `in`
 (sorted; `data['rgb'][0][0]` uint8 [H,W,3], `data['calib'][0][0]` 3x3 with K = calib.T) goes through the network at its native
@@ -47,8 +50,13 @@ def parse_args(argv=None):
     p.add_argument("--score_threshold", default=0.3, type=float)
     p.add_argument("--depth_mode", default="colored", type=str, choices=["colored", "gray"])
     p.add_argument("--depth_shift", default=512, type=float)
+    p.add_argument("--render", default="host", type=str, choices=["host", "device"],
+                   help="where masks, boxes and the depth picture are drawn: host (numpy + Pillow) or device (planerecnet_amd.render: one uint8 image each comes back)")
+    p.add_argument("--contours", action="store_true", help="white one-pixel mask outlines (--render device only)")
     global args
     args = p.parse_args(argv)
+    if args.contours and args.render != "device":
+        p.error("--contours needs --render device")
     return args
 
 
@@ -92,6 +100,26 @@ def display_on_frame(result, frame, mask_alpha=0.5, no_mask=False, no_box=False,
     return np.asarray(pil)[:, :, ::-1], depth
 
 
+def display_on_device(result, frame, depth_mode="colored", depth_shift=512, no_mask=False, no_box=False, no_text=False, contours=False):
+    """display_on_frame and the depth picture with the drawing on the device (planerecnet_amd.render): masks, outlines, boxes and the
+    depth colours are made there, ONE uint8 image and ONE depth image are downloaded; the score texts are then drawn on the downloaded
+    image by Pillow -- all of them after all boxes (display_on_frame draws text i before box i + 1, so a later box can cross an earlier
+    text there).  -> (uint8 HxWx3 BGR, depth image: uint8 HxWx3 BGR or uint16 HxW)"""
+    from planerecnet_amd import render
+    seg = render.render_overlay(result, frame, no_mask=no_mask, no_box=no_box, contours=contours)
+    dep = render.colorize_depth(result["pred_depth"], mode=depth_mode, depth_shift=depth_shift)
+    seg, dep = seg.cpu().numpy(), dep.cpu().numpy()
+    if not no_text and result["pred_scores"] is not None:
+        from PIL import Image, ImageDraw
+        pil = Image.fromarray(seg[:, :, ::-1])
+        draw = ImageDraw.Draw(pil)
+        boxes, scores = result["pred_boxes"].cpu().numpy(), result["pred_scores"].cpu().numpy()
+        for i in range(scores.shape[0]):
+            draw.text((int(boxes[i][0]) + 2, int(boxes[i][1]) + 2), "plane: %.2f" % scores[i], fill=(255, 255, 255))
+        seg = np.asarray(pil)[:, :, ::-1]
+    return seg, dep
+
+
 def _viridis(depth, vmin, vmax):
     """depth clipped to [vmin, vmax], stretched to 0..255 and mapped through a 5-stop viridis ramp -> uint8 [H,W,3] RGB"""
     d = depth.clip(min=vmin, max=vmax)
@@ -111,10 +139,16 @@ def inference_image(net, path, save_path=None, depth_mode="colored"):
         staged = staged.pin_memory()
     batch, frame = frame_to_input(staged.to(cfg.device, non_blocking=True), calc_size_preserve_ar(W, H, cfg.max_size))
     results = net(batch)
-    blended, depth = display_on_frame(results[0], frame, no_mask=args.no_mask, no_box=args.no_box, no_text=args.no_text)
     name, ext = os.path.splitext(path if save_path is None else save_path)
     save_path = name + "_seg" + ext if save_path is None else save_path
     depth_path = name + "_dep.png"
+    if args.render == "device":
+        blended, depth_image = display_on_device(results[0], frame, depth_mode=depth_mode, depth_shift=args.depth_shift, no_mask=args.no_mask,
+                                                 no_box=args.no_box, no_text=args.no_text, contours=args.contours)
+        _imwrite_bgr(save_path, blended)
+        _imwrite_bgr(depth_path, depth_image)
+        return results
+    blended, depth = display_on_frame(results[0], frame, no_mask=args.no_mask, no_box=args.no_box, no_text=args.no_text)
     _imwrite_bgr(save_path, blended)
     if depth_mode == "colored":
         vmin, vmax = np.percentile(depth, 1), np.percentile(depth, 99)
