@@ -9,10 +9,14 @@ prn_depth_metrics, prn_pairwise_iou); only the per-threshold matching and the AP
 operations -- run on the host.
 
 Outside this build (they need cv2 / pycocotools / tensorboardX): the annotated dataset readers -- frames come from
-`--dataset synthetic` (planerecnet_amd/datasets.py) -- and `--autopsy`.  `--output_coco_json`, `--bbox_det_file` and
-`--mask_det_file` are parsed and unused, exactly as in the reference.
+`--dataset synthetic` (planerecnet_amd/datasets.py) -- and `--autopsy`.
+
+`--output_coco_json` writes every detection of every evaluated frame as COCO result files (YOLACT's `Detections`; the reference parses
+the flag and drops it): boxes to `--bbox_det_file`, masks to `--mask_det_file` as compressed run-length strings coded on the device
+(planerecnet_amd/rle.py; include/prn.h: prn_rle_*) -- the masks themselves never leave the GPU.  Without the flag nothing is collected.
 """
 import argparse
+import json
 import os
 import random
 import time
@@ -35,9 +39,12 @@ def parse_args(argv=None):
     parser.add_argument("--top_k", default=100, type=int, help="Further restrict the number of predictions to parse")
     parser.add_argument("--score_threshold", default=0.15, type=float, help="Detections with a score under this threshold will not be considered.")
     parser.add_argument("--nms_mode", default="matrix", type=str, choices=["matrix", "mask"], help="Chose NMS type from matrix and mask nms.")
-    parser.add_argument("--output_coco_json", dest="output_coco_json", action="store_true", help="(parsed, unused -- as in the reference)")
-    parser.add_argument("--bbox_det_file", default="results/bbox_detections.json", type=str, help="(parsed, unused -- as in the reference)")
-    parser.add_argument("--mask_det_file", default="results/mask_detections.json", type=str, help="(parsed, unused -- as in the reference)")
+    parser.add_argument("--output_coco_json", dest="output_coco_json", action="store_true",
+                        help="Write the detections of the evaluated frames as COCO result files (see --bbox_det_file / --mask_det_file).")
+    parser.add_argument("--bbox_det_file", default="results/bbox_detections.json", type=str,
+                        help="With --output_coco_json: the file the box detections go to (image_id, category_id, bbox [x, y, w, h], score).")
+    parser.add_argument("--mask_det_file", default="results/mask_detections.json", type=str,
+                        help="With --output_coco_json: the file the mask detections go to (image_id, category_id, segmentation as COCO RLE, score).")
     parser.add_argument("--max_images", default=-1, type=int, help="The maximum number of images from the dataset to consider. Use -1 for all.")
     parser.add_argument("--config", default=None, help="The config object to use.")
     parser.add_argument("--no_bar", dest="no_bar", action="store_true", help="Do not output the status bar.")
@@ -54,8 +61,46 @@ def _bar(done, total, width=30):
     return "[" + "#" * filled + " " * (width - filled) + "]"
 
 
-def evaluate(net, dataset, during_training=False, eval_nums=-1):
-    """Reference eval.py:63-130.  Returns (mAP table as calc_map returns it, {metric name: mean over the frames})."""
+class Detections:
+    """The detections of the evaluated frames in COCO's result format (YOLACT eval.py: `Detections`): two lists, written as two JSON files.
+      bbox_data  {"image_id", "category_id", "bbox": [x, y, w, h], "score"}: pred_boxes (x0, y0, x1, y1) as [x0, y0, x1 - x0, y1 - y0], every
+                 value rounded to one decimal
+      mask_data  {"image_id", "category_id", "segmentation": {"size": [H, W], "counts": str}, "score"}: the mask as compressed RLE
+    `encode`: masks [N,H,W] -> N RLE dicts (default: planerecnet_amd.rle.encode, on the device)."""
+
+    def __init__(self, encode=None):
+        self.bbox_data, self.mask_data = [], []
+        self._encode = encode
+
+    def add_frame(self, image_id, result, label_map=None):
+        """every detection of one eval-mode result dict; a frame without detections adds nothing"""
+        masks = result.get("pred_masks")
+        if masks is None or result.get("pred_scores") is None or len(masks) == 0:
+            return
+        if self._encode is None:
+            from planerecnet_amd import rle
+            self._encode = rle.encode
+        rles = self._encode(masks)
+        boxes, classes, scores = (torch.as_tensor(result[k]).cpu().tolist() for k in ("pred_boxes", "pred_classes", "pred_scores"))
+        label_map = label_map or {}
+        image_id = image_id.item() if hasattr(image_id, "item") else image_id        # (a numpy / tensor scalar id: json takes plain ints)
+        for box, cls, score, seg in zip(boxes, classes, scores, rles):
+            category = label_map.get(int(cls) + 1, int(cls) + 1)
+            bbox = [box[0], box[1], box[2] - box[0], box[3] - box[1]]
+            self.bbox_data.append({"image_id": image_id, "category_id": category, "bbox": [round(float(v) * 10) / 10 for v in bbox], "score": float(score)})
+            self.mask_data.append({"image_id": image_id, "category_id": category, "segmentation": {"size": list(seg["size"]), "counts": seg["counts"]},
+                                   "score": float(score)})
+
+    def dump(self, bbox_file, mask_file):
+        for data, path in ((self.bbox_data, bbox_file), (self.mask_data, mask_file)):
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            with open(path, "w") as f:
+                json.dump(data, f)
+
+
+def evaluate(net, dataset, during_training=False, eval_nums=-1, detections=None):
+    """Reference eval.py:63-130.  Returns (mAP table as calc_map returns it, {metric name: mean over the frames}).
+    detections: a `Detections` collector every frame's detections are added to (eval.py --output_coco_json; train.py passes none)."""
     from planerecnet_amd import metrics
     if args is None:
         parse_args(["--no_bar"])                                    # train.py's setup_eval (reference train.py:436-437)
@@ -78,6 +123,9 @@ def evaluate(net, dataset, during_training=False, eval_nums=-1):
             if result["pred_masks"] is not None:
                 metrics.compute_segmentation_metrics(ap_data, gt_masks, gt_boxes, gt_classes, result["pred_masks"], result["pred_boxes"],
                                                      result["pred_classes"], result["pred_scores"])
+                if detections is not None:
+                    image_id = dataset.ids[image_idx] if hasattr(dataset, "ids") else image_idx
+                    detections.add_frame(image_id, result, getattr(cfg.dataset, "label_map", None))
             torch.cuda.synchronize(dev)
             if it > 1:                                              # the first frames include one-time setup (reference :103-106)
                 frame_times.add(time.perf_counter() - t0)
@@ -144,7 +192,11 @@ def main():
         print(" done.")
         cfg.device = "cuda:0"
         net = net.to("cuda:0")
-        evaluate(net, dataset, during_training=False, eval_nums=args.max_images)
+        detections = Detections() if args.output_coco_json else None
+        evaluate(net, dataset, during_training=False, eval_nums=args.max_images, detections=detections)
+        if detections is not None:
+            detections.dump(args.bbox_det_file, args.mask_det_file)
+            print("Wrote %d detections to %s and %s" % (len(detections.bbox_data), args.bbox_det_file, args.mask_det_file))
 
 
 if __name__ == "__main__":

@@ -779,6 +779,33 @@ int prn_render_depth_limits(const float* depth, int64_t n, double q_lo, double q
 int prn_render_depth_colors(const float* depth, int64_t n, const float* limits, const unsigned char* lut, unsigned char* out, void* stream);
 int prn_render_depth_gray(const float* depth, int64_t n, float shift, unsigned short* out, void* stream);
 
+/* ---- COCO run-length masks: the codec every COCO tool exchanges masks in (csrc/prn_rle.hip) ---------------------------------------
+ * A mask [H][W] is walked COLUMN-major, p = x * H + y, non-zero = set; its counts are the lengths of the runs of alternating value starting
+ * with a run of zeros (first count 0 when m[0][0] is set); the string codes count i (i > 2: minus count i-2) as 5-bit groups, least
+ * significant first, in characters 48 + group, bit 0x20 = another group follows, bit 0x10 of the last group = the sign.
+ * The masks are a ragged batch as in prn_planes_fit: masks_dev a DEVICE array [B] of pointers to [N_b][H][W] bytes, first_dev a DEVICE
+ * array [B+1] of instance offsets; they are only read, row-major (4-byte loads where W % 4 == 0 and an image's base is 4-byte aligned).
+ * A mask with K run boundaries has K + 1 counts.  Encoding is four steps, the caller sizing each step's output from the previous one:
+ *   prn_rle_count           totals [Ntot] int = K of every mask; ws (prn_rle_ws_bytes, 4-byte aligned) keeps the rank of every (mask,
+ *                           column, 32-row segment) for prn_rle_fill.  Two launches.
+ *   prn_rle_fill            pos [pos_first[Ntot]] uint32: the boundary positions p of mask n, ascending, from pos_first[n] (DEVICE array
+ *                           [Ntot+1] int64, the running sum of totals).  One launch; a slot outside a mask's own range is never written.
+ *   prn_rle_string_lengths  str_len [Ntot] int64 = characters of every mask's string.  One launch.
+ *   prn_rle_strings         out [str_first[Ntot]] bytes: the strings, mask n from str_first[n] (DEVICE array [Ntot+1] int64, the running
+ *                           sum of str_len), no terminators.  One launch.
+ * prn_rle_paint (decoding): ends = every mask's cumulative run ends (uint32, ascending, the last one H W), mask n from end_first[n]
+ * (DEVICE array [Ntot+1] int64) -> out [Ntot][H][W] bytes, out[n][y][x] = (number of ends <= x * H + y) & 1; every byte is written,
+ * row-major (4-byte stores where W % 4 == 0 and out is 4-byte aligned).  One launch; Ntot <= 65535.
+ * All of it is integer arithmetic without atomics: results are identical run to run.  H, W, Ntot > 0 and H * W < 2^31 or the call is
+ * refused (prn_rle_ws_bytes: -1).  No allocation and no synchronisation inside. */
+int64_t prn_rle_ws_bytes(int Ntot, int H, int W);
+int prn_rle_count(const unsigned char* const* masks_dev, const int* first_dev, int B, int Ntot, int H, int W, void* ws, int* totals, void* stream);
+int prn_rle_fill(const unsigned char* const* masks_dev, const int* first_dev, int B, int Ntot, int H, int W, const void* ws, const int64_t* pos_first,
+                 unsigned* pos, void* stream);
+int prn_rle_string_lengths(const unsigned* pos, const int64_t* pos_first, int Ntot, int H, int W, int64_t* str_len, void* stream);
+int prn_rle_strings(const unsigned* pos, const int64_t* pos_first, const int64_t* str_first, int Ntot, int H, int W, unsigned char* out, void* stream);
+int prn_rle_paint(const unsigned* ends, const int64_t* end_first, int Ntot, int H, int W, unsigned char* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

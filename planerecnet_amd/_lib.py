@@ -211,6 +211,12 @@ SIGNATURES = {
     "prn_render_depth_limits": (c_int, [P, c_i64, ctypes.c_double, ctypes.c_double, P, P, P]),
     "prn_render_depth_colors": (c_int, [P, c_i64, P, P, P, P]),
     "prn_render_depth_gray": (c_int, [P, c_i64, c_float, P, P]),
+    "prn_rle_ws_bytes": (c_i64, [c_int] * 3),
+    "prn_rle_count": (c_int, [P, P] + [c_int] * 4 + [P, P, P]),
+    "prn_rle_fill": (c_int, [P, P] + [c_int] * 4 + [P, P, P, P]),
+    "prn_rle_string_lengths": (c_int, [P, P] + [c_int] * 3 + [P, P]),
+    "prn_rle_strings": (c_int, [P, P, P] + [c_int] * 3 + [P, P]),
+    "prn_rle_paint": (c_int, [P, P] + [c_int] * 3 + [P, P]),
 }
 
 
