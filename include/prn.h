@@ -448,7 +448,8 @@ int prn_sum_rows(const float* in, float* out, int nb, int R, int N, void* stream
  * only the weight-gradient family is measured this way); bits 8-15 issue the same families TWICE (idempotent launches: results unchanged; the step's
  * increase is the family's cost on the critical path, second read partly from the Infinity Cache).  Never called by the package; returns the old mask.
  * family bit 1: the forward BatchNorm statistics pass of the two-launch (large-map) form; 2: its backward counterpart; 4: the sums of weight-gradient
- * split partials (reduce_splits); 8: prn_channel_sum; 16: the exact x0.5 resize and its adjoint (models/fpn.py:54). */
+ * split partials (reduce_splits); 8: prn_channel_sum; 16: the exact x0.5 resize and its adjoint (models/fpn.py:54).
+ * Bits 16-18 leave a stage of prn_mask_nms out (pack, pairs, sweep): tools/mask_nms_bench.py times each stage alone on the buffers a full call left. */
 int prn_debug_skip_launches(int mask);
 
 /* ---- resampling ---------------------------------------------------------------------------------------------------
@@ -672,6 +673,18 @@ int prn_sigmoid_point_nms(const float* x, float* out, int B, int C, int S, int64
  * gaussian (exp(-sigma x^2)) or linear (1 - x) -- the dense torch form's ~15 [n, n] passes in two launches, same operations per element.
  * ws: n floats. */
 int prn_matrix_nms(const float* iou, const int64_t* labels, const float* scores, int n, float sigma, int gaussian, float* out, float* ws, void* stream);
+/* Greedy mask NMS (models/functions/nms.py:53-81) of a ragged batch (csrc/prn_mask_nms.hip).  masks [N, HW] byte masks (non-zero = set), labels [N],
+ * sum_masks [N] the CALLER's mask areas; seg: DEVICE table of n_img + 1 ascending offsets, image b owns the candidates [seg[b], seg[b+1]) in
+ * descending score order (empty segments allowed); n_max: the largest segment (sizes the grids).  Within an image, for i < j both still kept and
+ * of one label:  inter = |mask_i & mask_j| (exact),  union = (sum_masks[i] + sum_masks[j]) - inter  in fp32;  j is removed if union <= 0 or
+ * inter / union > thr (fp32 quotient, fp32 comparison) -- a removed candidate removes nobody.  keep [N] bytes: 1 kept, 0 removed.
+ * Three launches (bit-pack, pairwise suppression words, one greedy sweep per image); ws: prn_mask_nms_ws_bytes(n_total, n_max, HW) bytes,
+ * 8-byte aligned, n_total = seg[n_img].  Limits: n_max <= PRN_MASK_NMS_MAX candidates per image (64 lanes x 64 bits: one wave holds an image's
+ * removed set), 0 < HW < 2^24, n_img <= 65535. */
+#define PRN_MASK_NMS_MAX 4096
+int64_t prn_mask_nms_ws_bytes(int n_total, int n_max, int64_t HW);
+int prn_mask_nms(const unsigned char* masks, const int64_t* labels, const float* sum_masks, const int* seg, int n_img, int n_max, int64_t HW, float thr,
+                 unsigned char* keep, void* ws, void* stream);
 
 /* ---- GT-only preparation of the loss on the device (csrc/prn_targets.hip) ---------------------------------------------------
  * The per-instance mask work of SOLOv2's target assignment (models/functions/losses.py:200-286: centre of mass, empty-mask flag,

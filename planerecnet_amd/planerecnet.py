@@ -23,7 +23,8 @@ from .backbone import can_fold, construct_backbone, conv_bn, folded_bn
 from .config import cfg
 from .fpn import FPN
 from .funcs import bias_init_with_prob
-from .nms import mask_nms, matrix_nms
+from . import nms
+from .nms import matrix_nms
 
 
 _COORD = {}
@@ -263,12 +264,26 @@ class PlaneRecNet(nn.Module):
         labels = labels.index_select(0, kept)
         scores = scores.index_select(0, kept) * (msum.index_select(0, kept) / sum_masks)       # mask-quality ("maskness") weighting
         seg_masks = seg > self.mask_threshold
-        boxes, o = [], 0
+        boxes, o, sorted_imgs = [], 0, []
         for b in range(B):
             if n_img[b]:
                 sl = slice(o, o + n_img[b])
                 o += n_img[b]
-                boxes.append(self._finish_image(results[b], seg[sl], seg_masks[sl], sum_masks[sl], scores[sl], labels[sl], ori_size))
+                if self.nms_type == "mask":
+                    sorted_imgs.append((results[b],) + self._sort_image(seg[sl], seg_masks[sl], sum_masks[sl], scores[sl], labels[sl]))
+                else:
+                    boxes.append(self._finish_image(results[b], seg[sl], seg_masks[sl], sum_masks[sl], scores[sl], labels[sl], ori_size))
+        if sorted_imgs:
+            # greedy mask NMS of all images in ONE call on their sorted candidates (nms.mask_nms_batched), then the final selection per image
+            # (an entry: result, seg_preds, seg_masks [2], sum_masks [3], cate_scores [4], cate_labels [5])
+            one = len(sorted_imgs) == 1
+            counts = [int(s[4].shape[0]) for s in sorted_imgs]
+            keeps = nms.mask_nms_batched(sorted_imgs[0][5] if one else torch.cat([s[5] for s in sorted_imgs], 0),
+                                         sorted_imgs[0][2] if one else torch.cat([s[2] for s in sorted_imgs], 0),
+                                         sorted_imgs[0][3] if one else torch.cat([s[3] for s in sorted_imgs], 0), counts,
+                                         nms_thr=self.mask_threshold).split(counts)
+            for (result, seg_p, _, _, sc, lab), keep in zip(sorted_imgs, keeps):
+                boxes.append(self._select_image(result, seg_p, sc, lab, keep, ori_size))
         # boxes of all images in one transfer; returned on the CPU like the reference's default-device torch.zeros (quirk Q11)
         boxes = [(r, bx) for r, bx in boxes if bx is not None]
         if boxes:
@@ -277,19 +292,26 @@ class PlaneRecNet(nn.Module):
                 r["pred_boxes"] = h
         return results
 
-    def _finish_image(self, result, seg_preds, seg_masks, sum_masks, cate_scores, cate_labels, ori_size):
-        """Sort, NMS, final selection, full-size masks and (device) boxes of one image's candidates.  -> (result, boxes | None)"""
-        from .metrics import mask_boxes
+    def _sort_image(self, seg_preds, seg_masks, sum_masks, cate_scores, cate_labels):
+        """One image's candidates by descending score, the best max_before_nms of them.  -> (seg_preds, seg_masks, sum_masks, cate_scores, cate_labels)"""
         order = torch.argsort(cate_scores, descending=True)[: self.max_before_nms]
         seg_masks, seg_preds, sum_masks = seg_masks.index_select(0, order), seg_preds.index_select(0, order), sum_masks.index_select(0, order)
         cate_scores, cate_labels = cate_scores.index_select(0, order), cate_labels.index_select(0, order)
+        return seg_preds, seg_masks, sum_masks, cate_scores, cate_labels
+
+    def _finish_image(self, result, seg_preds, seg_masks, sum_masks, cate_scores, cate_labels, ori_size):
+        """Sort, NMS, final selection, full-size masks and (device) boxes of one image's candidates.  -> (result, boxes | None)"""
+        seg_preds, seg_masks, sum_masks, cate_scores, cate_labels = self._sort_image(seg_preds, seg_masks, sum_masks, cate_scores, cate_labels)
         if self.nms_type == "matrix":
             cate_scores = matrix_nms(cate_labels, seg_masks, sum_masks, cate_scores, sigma=self.nms_sigma, kernel=self.nms_kernel)
             keep = cate_scores >= self.update_threshold
-        elif self.nms_type == "mask":
-            keep = mask_nms(cate_labels, seg_masks, sum_masks, cate_scores, nms_thr=self.mask_threshold)
-        else:
+        else:                                                       # ("mask": batched by the caller)
             raise NotImplementedError
+        return self._select_image(result, seg_preds, cate_scores, cate_labels, keep, ori_size)
+
+    def _select_image(self, result, seg_preds, cate_scores, cate_labels, keep, ori_size):
+        """Final selection, full-size masks and (device) boxes of one image's sorted candidates after NMS.  -> (result, boxes | None)"""
+        from .metrics import mask_boxes
         kept = keep.nonzero(as_tuple=False).flatten()
         if kept.shape[0] == 0:
             return result, None
