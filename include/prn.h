@@ -449,7 +449,8 @@ int prn_sum_rows(const float* in, float* out, int nb, int R, int N, void* stream
  * increase is the family's cost on the critical path, second read partly from the Infinity Cache).  Never called by the package; returns the old mask.
  * family bit 1: the forward BatchNorm statistics pass of the two-launch (large-map) form; 2: its backward counterpart; 4: the sums of weight-gradient
  * split partials (reduce_splits); 8: prn_channel_sum; 16: the exact x0.5 resize and its adjoint (models/fpn.py:54).
- * Bits 16-18 leave a stage of prn_mask_nms out (pack, pairs, sweep): tools/mask_nms_bench.py times each stage alone on the buffers a full call left. */
+ * Bits 16-18 leave a stage of prn_mask_nms out (pack, pairs, sweep): tools/mask_nms_bench.py times each stage alone on the buffers a full call left.
+ * Bits 19-24 leave a launch family of prn_ccl_* out (local, seam, flatten, reduce, rank, write): tools/components_bench.py does the same. */
 int prn_debug_skip_launches(int mask);
 
 /* ---- resampling ---------------------------------------------------------------------------------------------------
@@ -818,6 +819,37 @@ int prn_rle_fill(const unsigned char* const* masks_dev, const int* first_dev, in
 int prn_rle_string_lengths(const unsigned* pos, const int64_t* pos_first, int Ntot, int H, int W, int64_t* str_len, void* stream);
 int prn_rle_strings(const unsigned* pos, const int64_t* pos_first, const int64_t* str_first, int Ntot, int H, int W, unsigned char* out, void* stream);
 int prn_rle_paint(const unsigned* ends, const int64_t* end_first, int Ntot, int H, int W, unsigned char* out, void* stream);
+
+/* ---- connected components of instance masks: labels, and masks cleaned to one region (csrc/prn_ccl.hip) --------------------------
+ * A mask is [H][W] bytes, non-zero = set; connectivity is 8 or 4.  A component is a maximal set of set pixels connected under it; the
+ * components of a mask are numbered 1..K in ascending order of their smallest row-major index y * W + x -- scipy.ndimage.label with the
+ * full 3x3 structure (8) or the cross (4).  The masks are a ragged batch as in prn_planes_fit / prn_rle_*: masks_dev a DEVICE array [B] of
+ * pointers to [N_b][H][W] bytes, first_dev a DEVICE array [B+1] of instance offsets, Ntot = first_dev[B] given by the host; only read.
+ *   prn_ccl_label   labels [Ntot][H][W] int32 (0 on unset pixels), count [Ntot] int32 = K.  Six launches.
+ *   prn_ccl_clean   per mask, in this order: (1) label it and take every component's area; (2) keep_all == 0: keep the component of
+ *                   maximal area, on a tie the lowest label, nothing if that area < min_area; keep_all != 0: keep every component of area
+ *                   >= min_area; (3) fill_holes != 0: in the mask SELECTED by (2) -- not the input: removing a speck inside a hole changes
+ *                   which holes exist -- every unset pixel becomes set unless unset pixels connect it to an unset pixel on the image
+ *                   border under the dual connectivity (4 for 8, 8 for 4: scipy.ndimage.binary_fill_holes with the cross / the full
+ *                   structure).  out [Ntot][H][W] bytes (1 = set; every byte written), and four int32 [Ntot]: count = components of the
+ *                   input, kept = components kept, largest = area of the largest input component (0: empty mask), area = set pixels of
+ *                   out.  No mask is ever dropped: one that loses everything comes back empty.  Five launches, ten with fill_holes.
+ * One engine does all of it ("label the pixels whose value is v under connectivity c, keep components by a rule"): union-find per
+ * PRN_CCL_TILE_H x PRN_CCL_TILE_W tile in LDS, unions across the tile seams by global integer atomic min (the smaller index becomes the parent),
+ * a flatten pass that also takes areas and border contact by integer atomic add / or, a per-mask reduction, the write; the hole pass is
+ * the same launches on `out` with v = unset, and its result the complement of the components that touch the border.  No workgroup waits
+ * for another (the launch boundary is the only ordering), every loop is bounded by H * W, all atomics are integer: results are identical
+ * run to run and between a batched call and per-image calls.
+ * ws: prn_ccl_ws_bytes(Ntot, H, W) bytes, 8-byte aligned: one int32 per pixel per mask (the forest) + 32 bytes per mask + 4 bytes per
+ * (mask, 2048-pixel chunk).  H * W >= 2^31, Ntot > 65535 or a size <= 0 is refused (prn_ccl_ws_bytes: -1).  No allocation and no
+ * synchronisation inside; everything runs on `stream`. */
+#define PRN_CCL_TILE_H 32
+#define PRN_CCL_TILE_W 64
+int64_t prn_ccl_ws_bytes(int Ntot, int H, int W);
+int prn_ccl_label(const unsigned char* const* masks_dev, const int* first_dev, int B, int Ntot, int H, int W, int connectivity, int* labels, int* count,
+                  void* ws, void* stream);
+int prn_ccl_clean(const unsigned char* const* masks_dev, const int* first_dev, int B, int Ntot, int H, int W, int connectivity, int keep_all, int min_area,
+                  int fill_holes, unsigned char* out, int* count, int* kept, int* largest, int* area, void* ws, void* stream);
 
 #ifdef __cplusplus
 }

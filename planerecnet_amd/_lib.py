@@ -219,6 +219,9 @@ SIGNATURES = {
     "prn_rle_string_lengths": (c_int, [P, P] + [c_int] * 3 + [P, P]),
     "prn_rle_strings": (c_int, [P, P, P] + [c_int] * 3 + [P, P]),
     "prn_rle_paint": (c_int, [P, P] + [c_int] * 3 + [P, P]),
+    "prn_ccl_ws_bytes": (c_i64, [c_int] * 3),
+    "prn_ccl_label": (c_int, [P, P] + [c_int] * 5 + [P, P, P, P]),
+    "prn_ccl_clean": (c_int, [P, P] + [c_int] * 8 + [P] * 7),
 }
 
 

@@ -107,7 +107,7 @@ def fit_planes(depth, masks, k_matrix):
 
 
 @torch.no_grad()
-def planar_depth(results, k_matrix, depth_range=None):
+def planar_depth(results, k_matrix, depth_range=None, clean=None):
     """The planar depth of PlaneRecNet's eval-mode output (the list of per-image dicts): for every image a NEW dict with the
     input's entries plus
        pred_planes      [N,4] fp64 (see fit_planes; [0,4] when the image has no detections)
@@ -115,14 +115,24 @@ def planar_depth(results, k_matrix, depth_range=None):
        pred_plane_depth [1,1,H,W] fp32: pred_depth with every pixel a valid instance covers replaced by the plane depth of the
                         highest-index valid covering instance (the lowest-scored one: detections come in descending score order)
     depth_range = (lo, hi): values <= lo or >= hi become NaN afterwards (the iBims-1 exporter uses (0, 10)).
+    clean = a dict of components.clean keywords (e.g. {"keep": "largest", "fill_holes": True}): every mask is cleaned on the device before the
+    fit and the composition -- a speck on another surface tilts the least-squares plane of the whole instance -- and the dicts gain
+       pred_plane_masks the masks that were used (pred_masks itself stays as it came)
+    clean = None: the masks are used as they are.
     The input dicts and their tensors are not modified."""
     depth = torch.cat([r["pred_depth"].reshape(1, 1, *r["pred_depth"].shape[-2:]) for r in results]).float()
-    f = _Fit(depth, [r.get("pred_masks") for r in results], k_matrix)
+    masks = [r.get("pred_masks") for r in results]
+    if clean is not None:
+        from . import components
+        masks = components.clean(masks, **clean)[0] if any(m is not None for m in masks) else masks
+    f = _Fit(depth, masks, k_matrix)
     out = f.render(depth_range)
     planes, valid = f.split(f.planes), f.split(f.valid)
     new = []
     for b, r in enumerate(results):
         d = dict(r)
         d["pred_planes"], d["pred_plane_valid"], d["pred_plane_depth"] = planes[b], valid[b], out[b:b + 1]
+        if clean is not None:
+            d["pred_plane_masks"] = masks[b]
         new.append(d)
     return new

@@ -53,11 +53,35 @@ def parse_args(argv=None):
     p.add_argument("--render", default="host", type=str, choices=["host", "device"],
                    help="where masks, boxes and the depth picture are drawn: host (numpy + Pillow) or device (planerecnet_amd.render: one uint8 image each comes back)")
     p.add_argument("--contours", action="store_true", help="white one-pixel mask outlines (--render device only)")
+    p.add_argument("--clean_masks", default="off", type=str, choices=["off", "largest", "all"],
+                   help="reduce every predicted mask to its largest connected component, or to all components of at least --min_area pixels, "
+                        "on the device (planerecnet_amd.components) before drawing and before the planar depth of --ibims1_pd")
+    p.add_argument("--min_area", default=0, type=int, help="--clean_masks: components smaller than this are removed")
+    p.add_argument("--fill_holes", action="store_true", help="--clean_masks: fill the holes of what was kept")
+    p.add_argument("--connectivity", default=8, type=int, choices=[4, 8], help="--clean_masks: pixel connectivity of a component")
     global args
     args = p.parse_args(argv)
     if args.contours and args.render != "device":
         p.error("--contours needs --render device")
+    if args.min_area < 0:
+        p.error("--min_area must be >= 0")
     return args
+
+
+def clean_options():
+    """the components.clean keywords the flags ask for (None: --clean_masks off)"""
+    if args.clean_masks == "off":
+        return None
+    return {"keep": args.clean_masks, "min_area": args.min_area, "fill_holes": args.fill_holes, "connectivity": args.connectivity}
+
+
+def cleaned(results):
+    """the network's results with the masks cleaned and the boxes recomputed where --clean_masks asks for it"""
+    opts = clean_options()
+    if opts is None:
+        return results
+    from planerecnet_amd.components import clean_results
+    return clean_results(results, **opts)
 
 
 def _imread_bgr(path):
@@ -138,7 +162,7 @@ def inference_image(net, path, save_path=None, depth_mode="colored"):
     if torch.cuda.is_available():
         staged = staged.pin_memory()
     batch, frame = frame_to_input(staged.to(cfg.device, non_blocking=True), calc_size_preserve_ar(W, H, cfg.max_size))
-    results = net(batch)
+    results = cleaned(net(batch))
     name, ext = os.path.splitext(path if save_path is None else save_path)
     save_path = name + "_seg" + ext if save_path is None else save_path
     depth_path = name + "_dep.png"
@@ -217,7 +241,7 @@ def _ibims1_export(net, in_folder, out_folder, planar):
         r = ibims1_results(net, rgb)
         if planar:
             from planerecnet_amd.planes import planar_depth
-            depth = planar_depth([r], k_matrix, depth_range=(0.0, 10.0))[0]["pred_plane_depth"]
+            depth = planar_depth([r], k_matrix, depth_range=(0.0, 10.0), clean=clean_options())[0]["pred_plane_depth"]
         else:
             depth = r["pred_depth"]
         depth = depth.squeeze().float().cpu().numpy()
