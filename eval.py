@@ -14,6 +14,11 @@ Outside this build (they need cv2 / pycocotools / tensorboardX): the annotated d
 `--output_coco_json` writes every detection of every evaluated frame as COCO result files (YOLACT's `Detections`; the reference parses
 the flag and drops it): boxes to `--bbox_det_file`, masks to `--mask_det_file` as compressed run-length strings coded on the device
 (planerecnet_amd/rle.py; include/prn.h: prn_rle_*) -- the masks themselves never leave the GPU.  Without the flag nothing is collected.
+
+`--boundary_ap` adds a third row, `bndry`, to the AP table: Boundary AP in COCO's form (Cheng et al., CVPR 2021), where a detection matches a
+ground-truth mask iff min(mask IoU, boundary IoU) exceeds the threshold.  The bands (`--boundary_ratio` of the image diagonal wide) are eroded
+and compared on the device (planerecnet_amd/morphology.py, metrics.boundary_iou; include/prn.h: prn_boundary_iou).  Without the flag the
+output is what it was.
 """
 import argparse
 import json
@@ -50,6 +55,10 @@ def parse_args(argv=None):
     parser.add_argument("--no_bar", dest="no_bar", action="store_true", help="Do not output the status bar.")
     parser.add_argument("--autopsy", dest="autopsy", action="store_true", help="(tensorboard image log: not part of this build)")
     parser.add_argument("--dataset", default=None, type=str, help="Override the config's dataset ('synthetic' for seeded synthetic frames).")
+    parser.add_argument("--boundary_ap", dest="boundary_ap", action="store_true",
+                        help="(extension) Add a Boundary AP row to the table: a detection matches iff min(mask IoU, boundary IoU) exceeds the threshold.")
+    parser.add_argument("--boundary_ratio", default=0.02, type=float,
+                        help="With --boundary_ap: the band width as a share of the image diagonal (Boundary IoU's dilation ratio).")
     parser.add_argument("--synthetic_size", default=16, type=int, help="(extension) frames in the synthetic dataset.")
     global args
     args = parser.parse_args(argv)
@@ -98,10 +107,12 @@ class Detections:
                 json.dump(data, f)
 
 
-def evaluate(net, dataset, during_training=False, eval_nums=-1, detections=None):
+def evaluate(net, dataset, during_training=False, eval_nums=-1, detections=None, boundary_ratio=None):
     """Reference eval.py:63-130.  Returns (mAP table as calc_map returns it, {metric name: mean over the frames}).
-    detections: a `Detections` collector every frame's detections are added to (eval.py --output_coco_json; train.py passes none)."""
+    detections: a `Detections` collector every frame's detections are added to (eval.py --output_coco_json; train.py passes none).
+    boundary_ratio: add the Boundary AP row (eval.py --boundary_ap); the band width of a frame is this share of its ground-truth masks' diagonal."""
     from planerecnet_amd import metrics
+    from planerecnet_amd.morphology import boundary_radius
     if args is None:
         parse_args(["--no_bar"])                                    # train.py's setup_eval (reference train.py:436-437)
     frame_times = MovingAverage()
@@ -111,7 +122,7 @@ def evaluate(net, dataset, during_training=False, eval_nums=-1, detections=None)
     random.shuffle(indices)
     indices = indices[:eval_nums]
     dev = next(net.parameters()).device
-    infos, ap_data, all_maps = [], metrics.new_ap_data(), None
+    infos, ap_data, all_maps = [], metrics.new_ap_data(boundary=boundary_ratio is not None), None
     try:
         for it, image_idx in enumerate(indices):
             torch.cuda.synchronize(dev)
@@ -121,8 +132,9 @@ def evaluate(net, dataset, during_training=False, eval_nums=-1, detections=None)
             gt_masks, gt_boxes, gt_classes = (gt_instances[k].to(dev) for k in ("masks", "boxes", "classes"))
             infos.append([float(v) for v in metrics.compute_depth_metrics(result["pred_depth"], gt_depth.to(dev), median_scaling=True)])
             if result["pred_masks"] is not None:
+                radius = None if boundary_ratio is None else boundary_radius(gt_masks.shape[-2], gt_masks.shape[-1], boundary_ratio)
                 metrics.compute_segmentation_metrics(ap_data, gt_masks, gt_boxes, gt_classes, result["pred_masks"], result["pred_boxes"],
-                                                     result["pred_classes"], result["pred_scores"])
+                                                     result["pred_classes"], result["pred_scores"], boundary_radius=radius)
                 if detections is not None:
                     image_id = dataset.ids[image_idx] if hasattr(dataset, "ids") else image_idx
                     detections.add_frame(image_id, result, getattr(cfg.dataset, "label_map", None))
@@ -193,7 +205,8 @@ def main():
         cfg.device = "cuda:0"
         net = net.to("cuda:0")
         detections = Detections() if args.output_coco_json else None
-        evaluate(net, dataset, during_training=False, eval_nums=args.max_images, detections=detections)
+        evaluate(net, dataset, during_training=False, eval_nums=args.max_images, detections=detections,
+                 boundary_ratio=args.boundary_ratio if args.boundary_ap else None)
         if detections is not None:
             detections.dump(args.bbox_det_file, args.mask_det_file)
             print("Wrote %d detections to %s and %s" % (len(detections.bbox_data), args.bbox_det_file, args.mask_det_file))

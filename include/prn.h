@@ -450,7 +450,8 @@ int prn_sum_rows(const float* in, float* out, int nb, int R, int N, void* stream
  * family bit 1: the forward BatchNorm statistics pass of the two-launch (large-map) form; 2: its backward counterpart; 4: the sums of weight-gradient
  * split partials (reduce_splits); 8: prn_channel_sum; 16: the exact x0.5 resize and its adjoint (models/fpn.py:54).
  * Bits 16-18 leave a stage of prn_mask_nms out (pack, pairs, sweep): tools/mask_nms_bench.py times each stage alone on the buffers a full call left.
- * Bits 19-24 leave a launch family of prn_ccl_* out (local, seam, flatten, reduce, rank, write): tools/components_bench.py does the same. */
+ * Bits 19-24 leave a launch family of prn_ccl_* out (local, seam, flatten, reduce, rank, write): tools/components_bench.py does the same.
+ * Bits 25-28 leave a launch family of prn_morph / prn_boundary_iou out (pack, row, column, pairs): tools/boundary_bench.py does the same. */
 int prn_debug_skip_launches(int mask);
 
 /* ---- resampling ---------------------------------------------------------------------------------------------------
@@ -850,6 +851,41 @@ int prn_ccl_label(const unsigned char* const* masks_dev, const int* first_dev, i
                   void* ws, void* stream);
 int prn_ccl_clean(const unsigned char* const* masks_dev, const int* first_dev, int B, int Ntot, int H, int W, int connectivity, int keep_all, int min_area,
                   int fill_holes, unsigned char* out, int* count, int* kept, int* largest, int* area, void* ws, void* stream);
+
+/* ---- erosion, dilation and the inner boundary of instance masks; the boundary IoU matrix (csrc/prn_morph.hip) ---------------------
+ * A mask is [H][W] bytes, non-zero = set.  The structuring element is the full (2 radius + 1)^2 square (= `radius` iterations of the 3 x 3
+ * all-ones element); pixels outside the image have the value `border` (0 or 1).  All results are integer-exact and coincide with
+ * scipy.ndimage.binary_erosion / binary_dilation(m, ones((3, 3)), iterations = radius, border_value = border):
+ *   PRN_MORPH_ERODE     a pixel is set iff every pixel of the square round it is set; radius 0 copies; radius >= max(H, W) is legal
+ *   PRN_MORPH_DILATE    set iff any pixel of the square is set  (= ~erode(~m, radius, 1 - border): the same launches on complemented words)
+ *   PRN_MORPH_BOUNDARY  m & ~erode(m, radius, border = 0): the inner band of Boundary IoU (Cheng et al., CVPR 2021).  `border` is ignored: the
+ *                       image edge counts as background, so a mask clipped by the frame has a band along the frame; radius 0: empty band
+ * prn_morph: the masks are a ragged batch as in prn_ccl_*: masks_dev a DEVICE array [B] of pointers to [N_b][H][W] bytes, first_dev a DEVICE
+ * array [B+1] of instance offsets, Ntot = first_dev[B] given by the host; only read.  out [Ntot][H][W] bytes, every byte written, 1 = set;
+ * area (optional) [Ntot] int32 = set pixels of out.  Three launches: pack to one bit per pixel with every row on a 64-bit word (ceil(W / 64)
+ * words per row), row pass (window AND by doubling; a shift carries across words), column pass over PRN_MORPH_TILE_ROWS x PRN_MORPH_TILE_WORDS
+ * word tiles -- rows and halo in 8 KB of LDS for min(radius, H) <= PRN_MORPH_LDS_RADIUS, straight from the workspace beyond -- which also
+ * writes the bytes and counts them.  ws: prn_morph_ws_bytes(Ntot, H, W, radius) bytes, 8-byte aligned (two packed copies).  H * W >= 2^31,
+ * Ntot > 65535, a size <= 0 or radius < 0 is refused (prn_morph_ws_bytes: -1).
+ * prn_boundary_iou: masks_a [A][H][W], masks_b [B][H][W] bytes -> two fp32 matrices [A][B] from one pair pass:
+ *   mask_iou (may be NULL) = |a & b| / ((|a| + |b|) - |a & b|), bit-identical to prn_pairwise_iou's;
+ *   boundary_iou           = the same expression on the bands boundary(a, radius), boundary(b, radius), which stay packed in ws.
+ * Integer counts, fp32 quotient, 0/0 = NaN.  ws: prn_boundary_iou_ws_bytes(A, B, H, W) bytes, 8-byte aligned.  1 <= A, B < 65536,
+ * H * W < 2^24, radius >= 0, or the call is refused (prn_boundary_iou_ws_bytes: -1).
+ * No workgroup waits for another, every loop is bounded by the sizes, the only atomics are integer adds: results are identical run to run
+ * and between a batched call and per-image calls.  No allocation and no synchronisation inside; everything runs on `stream`. */
+#define PRN_MORPH_ERODE 0
+#define PRN_MORPH_DILATE 1
+#define PRN_MORPH_BOUNDARY 2
+#define PRN_MORPH_TILE_ROWS 64
+#define PRN_MORPH_TILE_WORDS 4
+#define PRN_MORPH_LDS_RADIUS 32
+int64_t prn_morph_ws_bytes(int Ntot, int H, int W, int radius);
+int prn_morph(const unsigned char* const* masks_dev, const int* first_dev, int B, int Ntot, int H, int W, int op, int radius, int border, unsigned char* out,
+              int* area, void* ws, void* stream);
+int64_t prn_boundary_iou_ws_bytes(int A, int B, int H, int W);
+int prn_boundary_iou(const unsigned char* masks_a, const unsigned char* masks_b, int A, int B, int H, int W, int radius, float* mask_iou, float* boundary_iou,
+                     void* ws, void* stream);
 
 #ifdef __cplusplus
 }

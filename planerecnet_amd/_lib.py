@@ -222,6 +222,10 @@ SIGNATURES = {
     "prn_ccl_ws_bytes": (c_i64, [c_int] * 3),
     "prn_ccl_label": (c_int, [P, P] + [c_int] * 5 + [P, P, P, P]),
     "prn_ccl_clean": (c_int, [P, P] + [c_int] * 8 + [P] * 7),
+    "prn_morph_ws_bytes": (c_i64, [c_int] * 4),
+    "prn_morph": (c_int, [P, P] + [c_int] * 7 + [P] * 4),
+    "prn_boundary_iou_ws_bytes": (c_i64, [c_int] * 4),
+    "prn_boundary_iou": (c_int, [P, P] + [c_int] * 5 + [P] * 4),
 }
 
 

@@ -82,6 +82,34 @@ def pairwise_iou(masks_a=None, masks_b=None, boxes_a=None, boxes_b=None):
     return miou, biou
 
 
+def boundary_iou(masks_a, masks_b, radius=None, ratio=0.02):
+    """-> (mask_iou [A,B], boundary_iou [A,B]), fp32 device tensors, from one call (include/prn.h: prn_boundary_iou).  masks as for
+    `pairwise_iou`.  boundary_iou is the IoU of the inner bands m & ~erode(m, radius, border=0) (morphology.boundary; Cheng et al., CVPR
+    2021), which are built and compared bit-packed; mask_iou is bit-identical to pairwise_iou's.  radius=None: morphology.boundary_radius
+    of the mask size with `ratio`.  A pair of empty masks gives NaN in both."""
+    from .morphology import _check, boundary_radius
+    if not (torch.is_tensor(masks_a) and torch.is_tensor(masks_b) and masks_a.is_cuda and masks_a.dim() == 3 and masks_b.dim() == 3):
+        raise RuntimeError("boundary_iou needs [A,H,W] / [B,H,W] device tensors; there is no CPU path in the product")
+    if masks_a.shape[1:] != masks_b.shape[1:]:
+        raise RuntimeError("boundary_iou: mask sets of different size %s / %s" % (tuple(masks_a.shape), tuple(masks_b.shape)))
+    dev = masks_a.device
+    A, B, H, W = int(masks_a.shape[0]), int(masks_b.shape[0]), int(masks_a.shape[1]), int(masks_a.shape[2])
+    radius = boundary_radius(H, W, ratio) if radius is None else _check(radius, 0, "boundary_iou", tuple(masks_a.shape))[0]
+    if A == 0 or B == 0:
+        return torch.empty(A, B, device=dev), torch.empty(A, B, device=dev)
+    nbytes = lib.prn_boundary_iou_ws_bytes(A, B, H, W)
+    if nbytes < 0:
+        raise RuntimeError("boundary_iou: needs 1 <= A, B < 65536 and 0 < H * W < 2^24, got %s / %s" % (tuple(masks_a.shape), tuple(masks_b.shape)))
+    ma = (masks_a if masks_a.dtype in (torch.uint8, torch.bool) else masks_a != 0).contiguous().view(torch.uint8)
+    mb = (masks_b if masks_b.dtype in (torch.uint8, torch.bool) else masks_b != 0).to(dev).contiguous().view(torch.uint8)
+    out = torch.empty(2, A, B, device=dev)
+    ws = torch.empty((nbytes + 7) // 8 * 2, device=dev, dtype=torch.int32)
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
+    stream = ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index))
+    check(lib.prn_boundary_iou(ptr(ma), ptr(mb), A, B, H, W, radius, ptr(out[0]), ptr(out[1]), ptr(ws), stream), "prn_boundary_iou")
+    return out[0], out[1]
+
+
 def category_scores(cate_logits):
     """list of [B, C, S, S] category logits (one per grid level) -> [B, cells, C] scores after sigmoid + 2x2 point NMS, levels concatenated
     (reference planerecnet.py:113 + models/functions/nms.py:8-12 + the level concatenation of `inference`), one launch per level."""
@@ -192,17 +220,25 @@ class APDataObject:
         return sum(bars.tolist()) / 101                                               # left-to-right like the reference's sum()
 
 
-def new_ap_data():
-    return {"box": [APDataObject() for _ in iou_thresholds], "mask": [APDataObject() for _ in iou_thresholds]}     # eval.py:77-80
+def new_ap_data(boundary=False):
+    """boundary: a third list "boundary" (Boundary AP: a detection matches iff min(mask IoU, boundary IoU) exceeds the threshold)"""
+    data = {"box": [APDataObject() for _ in iou_thresholds], "mask": [APDataObject() for _ in iou_thresholds]}     # eval.py:77-80
+    if boundary:
+        data["boundary"] = [APDataObject() for _ in iou_thresholds]
+    return data
 
 
-def match_frame(ap_data, mask_iou_np, box_iou_np, scores, num_gt_for_class):
-    """Host half of compute_segmentation_metrics: push one frame's detections into `ap_data` given its [A,B] IoU matrices."""
+def match_frame(ap_data, mask_iou_np, box_iou_np, scores, num_gt_for_class, boundary_iou_np=None):
+    """Host half of compute_segmentation_metrics: push one frame's detections into `ap_data` given its [A,B] IoU matrices.
+    boundary_iou_np: also push the "boundary" objects, matched on min(mask IoU, boundary IoU) (COCO's Boundary AP; NaN never matches)."""
     scores = np.asarray(scores, np.float64)
     order = np.argsort(-scores, kind="stable")                                        # eval.py:217
     s = scores[order]
+    kinds = (("box", box_iou_np), ("mask", mask_iou_np))
+    if boundary_iou_np is not None:
+        kinds += (("boundary", np.minimum(mask_iou_np, boundary_iou_np)),)
     for t, thr in enumerate(iou_thresholds):
-        for kind, iou in (("box", box_iou_np), ("mask", mask_iou_np)):
+        for kind, iou in kinds:
             obj = ap_data[kind][t]
             obj.add_gt_positives(num_gt_for_class)
             matched = (iou[order] > thr).any(axis=1) if iou.shape[1] else np.zeros(len(order), bool)    # NaN (empty masks) never matches
@@ -213,21 +249,30 @@ def match_frame(ap_data, mask_iou_np, box_iou_np, scores, num_gt_for_class):
             obj.extend(np.repeat(s, reps).tolist(), flags.tolist())
 
 
-def compute_segmentation_metrics(ap_data, gt_masks, gt_boxes, gt_classes, pred_masks, pred_boxes, pred_classes, pred_scores):
+def compute_segmentation_metrics(ap_data, gt_masks, gt_boxes, gt_classes, pred_masks, pred_boxes, pred_classes, pred_scores, boundary_radius=None):
     """One frame's detections against its ground truth, for every IoU threshold, boxes and masks (reference eval.py:210-252;
     same argument list).  Two reference behaviours are kept on purpose: a matched detection counts as a hit AND as a miss, and
-    one ground-truth instance may be matched by several detections."""
-    miou, biou = pairwise_iou(pred_masks, gt_masks.to(pred_masks.device), pred_boxes, gt_boxes)
+    one ground-truth instance may be matched by several detections.
+    boundary_radius: also push the "boundary" objects of `ap_data` (new_ap_data(boundary=True)); the mask IoU then comes with the
+    boundary IoU from one prn_boundary_iou call, the box IoU from prn_pairwise_iou as before."""
     num_gt_for_class = int((torch.as_tensor(gt_classes) == 0).sum())                  # eval.py:234
-    match_frame(ap_data, miou.cpu().numpy(), biou.cpu().numpy(), torch.as_tensor(pred_scores).detach().cpu().numpy(), num_gt_for_class)
+    scores = torch.as_tensor(pred_scores).detach().cpu().numpy()
+    if boundary_radius is None:
+        miou, biou = pairwise_iou(pred_masks, gt_masks.to(pred_masks.device), pred_boxes, gt_boxes)
+        match_frame(ap_data, miou.cpu().numpy(), biou.cpu().numpy(), scores, num_gt_for_class)
+        return
+    miou, bdiou = boundary_iou(pred_masks, gt_masks.to(pred_masks.device), radius=boundary_radius)
+    biou = pairwise_iou(boxes_a=pred_boxes.to(pred_masks.device), boxes_b=gt_boxes)[1]
+    match_frame(ap_data, miou.cpu().numpy(), biou.cpu().numpy(), scores, num_gt_for_class, boundary_iou_np=bdiou.cpu().numpy())
 
 
 def calc_map(ap_data, quiet=False):
-    """-> {'box': {'all', 50, 55, ..., 95}, 'mask': {...}} in percent, rounded to two decimals (reference eval.py:327-354)."""
+    """-> {'box': {'all', 50, 55, ..., 95}, 'mask': {...}} in percent, rounded to two decimals (reference eval.py:327-354); a 'boundary' row
+    iff `ap_data` has the key."""
     if not quiet:
         print("Calculating mAP...")
     all_maps = {}
-    for kind in ("box", "mask"):
+    for kind in ("box", "mask") + (("boundary",) if "boundary" in ap_data else ()):
         row = OrderedDict([("all", 0)])
         for t, thr in enumerate(iou_thresholds):
             obj = ap_data[kind][t]
@@ -240,14 +285,15 @@ def calc_map(ap_data, quiet=False):
 
 
 def print_maps(all_maps):
-    """The reference's table layout (eval.py:356-370)."""
+    """The reference's table layout (eval.py:356-370); the 'boundary' row, where there is one, is labelled 'bndry' (the cell is five wide)."""
     keys = list(all_maps["box"].keys())
     cell = " %5s |"
     rule = "-------+" * (len(keys) + 1)
     print()
     print(cell * (len(keys) + 1) % tuple([""] + [(".%d " % k) if isinstance(k, int) else k + " " for k in keys]))
     print(rule)
-    for kind in ("box", "mask"):
-        print(cell * (len(keys) + 1) % tuple([kind] + [("%.2f" % v) if v < 100 else ("%.1f" % v) for v in all_maps[kind].values()]))
+    for kind in ("box", "mask") + (("boundary",) if "boundary" in all_maps else ()):
+        name = "bndry" if kind == "boundary" else kind
+        print(cell * (len(keys) + 1) % tuple([name] + [("%.2f" % v) if v < 100 else ("%.1f" % v) for v in all_maps[kind].values()]))
     print(rule)
     print()
