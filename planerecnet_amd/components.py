@@ -21,31 +21,11 @@ import ctypes
 import numpy as np
 import torch
 
+from ._masks import _as_bytes, _bytes_buffer, _inputs, _p, _split, _stream, ragged_chunks
+
 __all__ = ["label", "clean", "clean_results", "TILE"]
 
 TILE = (32, 64)          # rows x columns of the tile one workgroup labels in LDS (include/prn.h: PRN_CCL_TILE_H / PRN_CCL_TILE_W)
-MAX_MASKS = 65535        # masks per library call
-
-
-def _describe(m):
-    return "%s %s %s" % (m.device, m.dtype, tuple(m.shape)) if torch.is_tensor(m) else type(m).__name__
-
-
-def _inputs(masks, what):
-    """-> (is_list, parts): parts[b] = None or a [N_b,H,W] bool / uint8 tensor; one device, one dtype, one H x W"""
-    is_list = isinstance(masks, (list, tuple))
-    parts = list(masks) if is_list else [masks]
-    ref = None
-    for b, m in enumerate(parts):
-        if m is None and is_list:
-            continue
-        if not (torch.is_tensor(m) and m.dim() == 3 and m.dtype in (torch.bool, torch.uint8)):
-            raise RuntimeError("%s: masks%s must be a bool / uint8 [N,H,W] tensor, got %s" % (what, "[%d]" % b if is_list else "", _describe(m)))
-        if ref is None:
-            ref = m
-        elif m.device != ref.device or m.dtype != ref.dtype or m.shape[1:] != ref.shape[1:]:
-            raise RuntimeError("%s: masks[%d] is %s, masks before it %s (one device, dtype and H x W per call)" % (what, b, _describe(m), _describe(ref)))
-    return is_list, parts, ref
 
 
 def _check_connectivity(connectivity, what):
@@ -131,75 +111,18 @@ def _clean_np(m, connectivity, keep, min_area, fill_holes):
 
 # ---- device path -----------------------------------------------------------------------------------------------------------------
 
-def _upload(values, dtype, device):
-    """host values -> device tensor through page-locked memory (an asynchronous copy: no host synchronisation)"""
-    return torch.tensor(values, dtype=dtype).pin_memory().to(device, non_blocking=True)
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def _bytes_buffer(n, device):
-    """n bytes as a view of an int32 allocation (4-byte allocations are what the suite's guard mode brackets)"""
-    return torch.empty((n + 3) // 4, dtype=torch.int32, device=device).view(torch.uint8)[:n]
-
-
-def _device_chunks(parts, H, W, max_workspace_bytes, what):
-    """The masks of all images as chunks the workspace limit admits: yields (g0, g1, pointers, first) -- global mask range, the byte
-    address of each contributing image's first mask in the range, and their running counts.  Sizes are host knowledge: no readback."""
-    from ._lib import lib
-    per_mask = lib.prn_ccl_ws_bytes(1, H, W)
-    if per_mask < 0:
-        raise RuntimeError("%s: H * W must be below 2^31, got %d x %d" % (what, H, W))
-    cap = int(max(1, min(MAX_MASKS, int(max_workspace_bytes) // per_mask)))
-    first = [0]
-    for m in parts:
-        first.append(first[-1] + int(m.shape[0]))
-    HW = H * W
-    for g0 in range(0, first[-1], cap):
-        g1 = min(first[-1], g0 + cap)
-        ptrs, cnt = [], [0]
-        for b, m in enumerate(parts):
-            lo, hi = max(g0, first[b]), min(g1, first[b + 1])
-            if lo < hi:
-                ptrs.append(m.data_ptr() + (lo - first[b]) * HW)
-                cnt.append(cnt[-1] + hi - lo)
-        yield g0, g1, ptrs, cnt
-
-
-def _device_run(parts, connectivity, what, max_workspace_bytes, call):
+def _device_run(parts, what, max_workspace_bytes, call):
     """parts: contiguous uint8 [N_b,H,W] device tensors with N_b > 0.  call(lib, ptrs_dev, first_dev, B, n, H, W, g0, ws, stream) per chunk."""
     from ._lib import lib
     dev = parts[0].device
     H, W = int(parts[0].shape[1]), int(parts[0].shape[2])
-    stream = ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index))
-    for g0, g1, ptrs, cnt in _device_chunks(parts, H, W, max_workspace_bytes, what):
-        n = g1 - g0
-        nbytes = lib.prn_ccl_ws_bytes(n, H, W)
-        ws = torch.empty((nbytes + 7) // 8 * 2, dtype=torch.int32, device=dev)
-        ptrs_dev, first_dev = _upload(ptrs, torch.int64, dev), _upload(cnt, torch.int32, dev)
-        call(lib, ptrs_dev, first_dev, len(ptrs), n, H, W, g0, ws, stream)
-        del ptrs_dev, first_dev, ws                                  # (stream-ordered allocator: reuse after this point is ordered behind the launches)
-
-
-def _as_bytes(m):
-    m = m.contiguous()
-    return m.view(torch.uint8) if m.dtype == torch.bool else m
-
-
-def _split(t, sizes, parts, is_list):
-    """a per-mask tensor over the non-empty images -> per-image outputs in input order (None stays None, N_b = 0 gives an empty tensor)"""
-    if not is_list:
-        return t
-    out, o = [], 0
-    for m, n in zip(parts, sizes):
-        if m is None:
-            out.append(None)
-        else:
-            out.append(t[o:o + n])
-            o += n
-    return out
+    per_mask = lib.prn_ccl_ws_bytes(1, H, W)
+    if per_mask < 0:
+        raise RuntimeError("%s: H * W must be below 2^31, got %d x %d" % (what, H, W))
+    for g0, g1, ptrs, first in ragged_chunks(parts, per_mask, max_workspace_bytes):
+        ws = torch.empty((lib.prn_ccl_ws_bytes(g1 - g0, H, W) + 7) // 8 * 2, dtype=torch.int32, device=dev)
+        call(lib, ptrs, first, ptrs.numel(), g1 - g0, H, W, g0, ws, _stream(dev))
+        del ptrs, first, ws                                          # (stream-ordered allocator: reuse after this point is ordered behind the launches)
 
 
 @torch.no_grad()
@@ -230,7 +153,7 @@ def label(masks, connectivity=8):
             def call(lib, ptrs, first, B, n, H, W, g0, ws, stream):
                 check(lib.prn_ccl_label(_p(ptrs), _p(first), B, n, H, W, connectivity, _p(labels[g0:]) if g0 else _p(labels),
                                         ctypes.c_void_p(count.data_ptr() + 4 * g0), _p(ws), stream), "prn_ccl_label")
-            _device_run(live, connectivity, "label", 256 << 20, call)
+            _device_run(live, "label", 256 << 20, call)
     if not is_list:
         return labels, count
     return _split(labels, sizes, parts, True), [c if c is not None else torch.zeros(0, dtype=torch.int32, device=dev) for c in _split(count, sizes, parts, True)]
@@ -278,7 +201,7 @@ def clean(masks, connectivity=8, keep="largest", min_area=0, fill_holes=False, m
                 s = [ctypes.c_void_p(st.data_ptr() + 4 * (k * Ntot + g0)) for k in range(4)]
                 check(lib.prn_ccl_clean(_p(ptrs), _p(first), B, n, H, W, connectivity, int(keep == "all"), min_area, int(bool(fill_holes)),
                                         ctypes.c_void_p(out.data_ptr() + g0 * H * W), s[0], s[1], s[2], s[3], _p(ws), stream), "prn_ccl_clean")
-            _device_run(live, connectivity, "clean", max_workspace_bytes, call)
+            _device_run(live, "clean", max_workspace_bytes, call)
         elif Ntot:
             st.zero_()
         if ref.dtype == torch.bool:

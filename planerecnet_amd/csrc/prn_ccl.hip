@@ -22,8 +22,7 @@
 //   and after the rank launch of prn_ccl_label a root's word is bit 31 | its label.
 // Launches (each on the caller's stream; the launch boundary is the only ordering between workgroups -- no flags, tickets or spins):
 //   local    a workgroup owns one (mask, 32 x 64 tile): union-find over the tile in LDS (decision tree over the N / W / NW / NE neighbours,
-//            unions by LDS atomic min), then P = the global index of every pixel's tile-local root.  Mask bytes come as 4-byte words only from
-//            4-byte aligned addresses inside the row (an odd mask base or W % 4 != 0 takes single bytes: the rule of prn_mask_nms's pack kernel).
+//            unions by LDS atomic min), then P = the global index of every pixel's tile-local root.  Mask bytes come four at a time (prn_masks.h).
 //   seam     one thread per pixel on a tile's left column / top row: union with its neighbours across the seam.  Reads are relaxed agent-scope
 //            atomic loads, writes atomic mins: the smaller index becomes the parent.  A stale parent is still a member of the same set at a
 //            larger index, so staleness costs steps, never correctness.
@@ -36,7 +35,7 @@
 // Every loop is bounded by H * W: a find follows strictly decreasing indices; a union retries only with the value its own atomic min returned,
 // which is smaller than the index it tried (the sum of the two indices falls with every retry).  All atomics are integer min / add / or / max:
 // the forest's final roots (the smallest index of each component), the areas and therefore every output byte are independent of arrival order.
-#include "prn_common.h"
+#include "prn_masks.h"
 
 namespace {
 
@@ -54,30 +53,6 @@ static_assert(PRN_CCL_TILE_H == CC_TH && PRN_CCL_TILE_W == CC_TW, "include/prn.h
 
 inline size_t cc_align8(size_t v) { return (v + 7) & ~(size_t)7; }
 inline int cc_chunks(int64_t HW) { return (int)((HW + CC_CHUNK - 1) / CC_CHUNK); }
-
-// where the masks of a pass come from: the caller's ragged batch, or (flat != NULL) [Ntot][H][W] bytes back to back
-struct cc_src {
-  const unsigned char* const* masks;
-  const int* first;
-  int B;
-  const unsigned char* flat;
-};
-
-__device__ __forceinline__ const unsigned char* cc_mask(const cc_src& s, int n, size_t HW) {
-  if (s.flat) return s.flat + (size_t)n * HW;
-  int lo = 0, hi = s.B - 1;
-  while (lo < hi) {                                                 // the last b with first[b] <= n (empty images are skipped)
-    const int mid = (lo + hi + 1) >> 1;
-    if (s.first[mid] <= n) lo = mid; else hi = mid - 1;
-  }
-  return s.masks[lo] + (size_t)(n - s.first[lo]) * HW;
-}
-
-__device__ __forceinline__ unsigned cc_nz4(unsigned v) {            // one bit per non-zero byte of v (bits 0..3)
-  v |= v >> 4; v |= v >> 2; v |= v >> 1;
-  v &= 0x01010101u;
-  return (v & 1u) | ((v >> 7) & 2u) | ((v >> 14) & 4u) | ((v >> 21) & 8u);
-}
 
 // ---- the forest in LDS (one tile) ----
 __device__ __forceinline__ int lds_load(const int* L, int x) { return __hip_atomic_load(L + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
@@ -123,12 +98,12 @@ __device__ __forceinline__ void g_union(int* P, int a, int b) {     // seam laun
 }
 
 // launch 1: grid (tiles, masks)
-__global__ __launch_bounds__(256) void ccl_local_kernel(cc_src src, int H, int W, int tiles_x, int vset, int conn8, int* __restrict__ P) {
+__global__ __launch_bounds__(256) void ccl_local_kernel(prn_mask_src src, int H, int W, int tiles_x, int vset, int conn8, int* __restrict__ P) {
   __shared__ int L[CC_TPIX];
   const int n = blockIdx.y, t = threadIdx.x;
   const int ty0 = (blockIdx.x / tiles_x) * CC_TH, tx0 = (blockIdx.x % tiles_x) * CC_TW;
   const size_t HW = (size_t)H * W;
-  const unsigned char* m = cc_mask(src, n, HW);
+  const unsigned char* m = prn_mask_ptr(src, n, HW);
   // stage: 512 groups of four pixels; pixels outside the image (never read) count as "not v"
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
@@ -136,14 +111,8 @@ __global__ __launch_bounds__(256) void ccl_local_kernel(cc_src src, int H, int W
     const int y = ty0 + ly, x = tx0 + lx;
     unsigned bits = 0;
     if (y < H && x < W) {
-      const unsigned char* p = m + (size_t)y * W + x;
       const int left = W - x;
-      if (left >= 4 && (reinterpret_cast<uintptr_t>(p) & 3) == 0) {
-        bits = cc_nz4(*reinterpret_cast<const unsigned*>(p));
-      } else {
-        const int cnt = left < 4 ? left : 4;
-        for (int j = 0; j < cnt; ++j) bits |= p[j] ? (1u << j) : 0u;
-      }
+      bits = prn_mask_bits4(m + (size_t)y * W + x, left);
       const unsigned inside = left >= 4 ? 15u : ((1u << left) - 1u);
       if (!vset) bits = ~bits & inside;
     }
@@ -267,12 +236,6 @@ __global__ __launch_bounds__(256) void ccl_flatten_kernel(int* __restrict__ P, i
 }
 
 __device__ __forceinline__ bool cc_is_root(int w, int i) { return w != CC_NONE && (w & CC_LOW) >= i; }
-
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // launch 4: grid (chunks, masks)
 __global__ __launch_bounds__(256) void ccl_reduce_kernel(const int* __restrict__ P, int64_t HW, int nchunk, int rule, int min_area, int* __restrict__ acc,
@@ -431,7 +394,7 @@ inline cc_ws cc_carve(void* ws, int Ntot, int64_t HW) {
 inline bool cc_sizes_ok(int Ntot, int H, int W) { return Ntot > 0 && Ntot <= 65535 && H > 0 && W > 0 && (int64_t)H * W < (1LL << 31); }
 
 // launches 1-4 of one pass.  skip: the measurement aid of include/prn.h (tools/components_bench.py times each launch alone)
-int cc_engine(const char* who, const cc_src& src, int Ntot, int H, int W, int vset, int conn8, int border, int rule, int min_area, const cc_ws& ws, hipStream_t st) {
+int cc_engine(const char* who, const prn_mask_src& src, int Ntot, int H, int W, int vset, int conn8, int border, int rule, int min_area, const cc_ws& ws, hipStream_t st) {
   const int64_t HW = (int64_t)H * W;
   const int tiles_x = cdiv(W, CC_TW), tiles_y = cdiv(H, CC_TH), nchunk = cc_chunks(HW);
   const int nvs = tiles_x - 1, nhs = tiles_y - 1;
@@ -470,7 +433,7 @@ extern "C" int prn_ccl_label(const unsigned char* const* masks_dev, const int* f
   const int64_t HW = (int64_t)H * W;
   const cc_ws w = cc_carve(ws, Ntot, HW);
   PRN_REQUIRE(hipMemsetAsync(w.acc, 0, (size_t)Ntot * CC_ACC * 4, st) == hipSuccess, "prn_ccl_label: memset failed");
-  const cc_src src = {masks_dev, first_dev, B, nullptr};
+  const prn_mask_src src = {masks_dev, first_dev, B, nullptr};
   if (int rc = cc_engine("prn_ccl_label", src, Ntot, H, W, 1, connectivity == 8, 0, RULE_NONE, 0, w, st)) return rc;
   const int nchunk = cc_chunks(HW);
   if (!PRN_SKIPPED(1 << 23)) hipLaunchKernelGGL(ccl_rank_kernel, dim3(nchunk, Ntot), dim3(256), 0, st, w.P, HW, nchunk, (const int*)w.chunks);
@@ -490,7 +453,7 @@ extern "C" int prn_ccl_clean(const unsigned char* const* masks_dev, const int* f
   const int64_t HW = (int64_t)H * W;
   const cc_ws w = cc_carve(ws, Ntot, HW);
   PRN_REQUIRE(hipMemsetAsync(w.acc, 0, (size_t)Ntot * CC_ACC * 4, st) == hipSuccess, "prn_ccl_clean: memset failed");
-  const cc_src src = {masks_dev, first_dev, B, nullptr};
+  const prn_mask_src src = {masks_dev, first_dev, B, nullptr};
   const int rule = keep_all ? RULE_MIN_AREA : RULE_LARGEST, conn8 = connectivity == 8;
   if (int rc = cc_engine("prn_ccl_clean", src, Ntot, H, W, 1, conn8, 0, rule, min_area, w, st)) return rc;
   if (!PRN_SKIPPED(1 << 24))
@@ -499,7 +462,7 @@ extern "C" int prn_ccl_clean(const unsigned char* const* masks_dev, const int* f
   PRN_CHECK_LAUNCH("prn_ccl_clean/write");
   if (fill_holes) {
     // the same engine on the selection: v = unset, the dual connectivity, rule "touches the border" (its own accumulator word)
-    const cc_src sel = {nullptr, nullptr, 0, out};
+    const prn_mask_src sel = {nullptr, nullptr, 0, out};
     if (int rc = cc_engine("prn_ccl_clean/holes", sel, Ntot, H, W, 0, !conn8, 1, RULE_BORDER, 0, w, st)) return rc;
     if (!PRN_SKIPPED(1 << 24))
       hipLaunchKernelGGL(ccl_write_holes_kernel, dim3(cdiv(HW, 256), Ntot), dim3(256), 0, st, (const int*)w.P, HW, (const int*)w.acc, out, area);

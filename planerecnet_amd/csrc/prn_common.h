@@ -93,6 +93,11 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
 
 // (a, b) summed over the workgroup in a fixed order (wave shuffles, then the waves' totals in wave order); sm: 2 * (waves per block) doubles
 __device__ __forceinline__ void block_sum2(double& a, double& b, double* sm) {
@@ -125,6 +130,7 @@ __device__ __forceinline__ void at6(const float* m, float* o) {
 }
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+__host__ __device__ inline size_t prn_align256(size_t v) { return (v + 255) & ~(size_t)255; }      // workspace sections start on 256 bytes
 
 // Internal (not part of the C ABI): the fixed-order split reductions of prn_conv.hip, shared with prn_dcnv2.hip.
 //   y = epi(sum_s ws[s] + bias[m] + addend)  over total = B*M*HoWo elements  /  out[i] = sum_s ws[s][i] over n elements

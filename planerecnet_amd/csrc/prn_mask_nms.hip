@@ -7,7 +7,7 @@
 //   pack   every mask to one bit per pixel, WORD-MAJOR within its image: word w of candidate j of image b (first candidate s_b, n_b
 //          candidates) sits at P[s_b * words + w * n_b + j].  A wave that puts one candidate per lane then loads word w of 64
 //          neighbouring candidates as one coalesced 256-byte access.  The transposition goes through an LDS tile, so the byte reads
-//          (64 threads over 2 KB of one mask) and the word writes (64 threads over 256 B of one word row) are both contiguous.
+//          (64 threads over 2 KB of one mask, 32 bytes each: prn_masks.h) and the word writes (64 threads over 256 B of one word row) are both contiguous.
 //   pairs  S[i][c], one 64-bit word per candidate i and block c of 64 columns: bit l = candidate j = 64 c + l is suppressed by i
 //          (i < j < n_b, equal labels, the decision above).  One column per lane, the decision balloted into the word; a workgroup
 //          takes 8 rows of one column block, its four waves a quarter of the mask words each, so a column word is loaded once for 8
@@ -18,35 +18,17 @@
 //          four waves while wave 0 works); the 64 keep-or-not decisions inside a block depend only on the diagonal words, lane r holding
 //          the one of row r: a chain of readlane / scalar steps without any memory access.  The surviving rows are then ORed into the
 //          removed set from LDS.
-#include "prn_common.h"
+#include "prn_masks.h"
 
 namespace {
 constexpr int MN_LIMIT = PRN_MASK_NMS_MAX;      // candidates per image: 64 lanes x 64 bits
 constexpr int MN_ROWS = 8;                      // rows of S per workgroup of the pairs kernel
 
 inline size_t mn_words(int64_t HW) { return (size_t)((HW + 31) / 32); }
-__host__ __device__ inline size_t mn_align256(size_t v) { return (v + 255) & ~(size_t)255; }
 // ws = the packed bits of all candidates | S.  Where S starts depends on the total number of candidates, which the entry point is not told:
 // the kernels read it from the end of the segment table.
 __device__ __forceinline__ size_t mn_s_offset(const int* __restrict__ seg, int n_img, int words) {
-  return mn_align256((size_t)seg[n_img] * words * 4);
-}
-
-// bits of the 32 pixels from `src` on (`left` of them exist; never reads past them)
-__device__ __forceinline__ unsigned mn_pack32(const unsigned char* __restrict__ src, int64_t left) {
-  unsigned word = 0;
-  if (left >= 32 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
-    const uint4 q0 = reinterpret_cast<const uint4*>(src)[0], q1 = reinterpret_cast<const uint4*>(src)[1];
-    const unsigned v[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) word |= ((v[k] >> (8 * b)) & 0xffu) ? (1u << (4 * k + b)) : 0u;
-  } else {
-    const int cnt = left < 32 ? (int)left : 32;
-    for (int i = 0; i < cnt; ++i) word |= src[i] ? (1u << i) : 0u;
-  }
-  return word;
+  return prn_align256((size_t)seg[n_img] * words * 4);
 }
 
 // grid (word tiles of 64, candidate tiles of 64, images)
@@ -61,7 +43,7 @@ __global__ __launch_bounds__(256) void mask_nms_pack_kernel(const unsigned char*
     const int e = threadIdx.x + 256 * q, ml = e >> 6, wl = e & 63;
     const int m = m0 + ml, w = w0 + wl;
     unsigned word = 0;
-    if (m < nb && w < words) word = mn_pack32(masks + (size_t)(s + m) * HW + (size_t)w * 32, HW - (int64_t)w * 32);
+    if (m < nb && w < words) word = prn_mask_bits32(masks + (size_t)(s + m) * HW + (size_t)w * 32, HW - (int64_t)w * 32);
     tile[ml][wl] = word;
   }
   __syncthreads();
@@ -189,7 +171,7 @@ __global__ __launch_bounds__(256) void mask_nms_sweep_kernel(const char* __restr
 
 extern "C" int64_t prn_mask_nms_ws_bytes(int n_total, int n_max, int64_t HW) {
   if (n_total <= 0 || n_max <= 0 || HW <= 0) return 256;
-  return (int64_t)(mn_align256((size_t)n_total * mn_words(HW) * 4) + (size_t)n_total * (size_t)((n_max + 63) / 64) * 8);
+  return (int64_t)(prn_align256((size_t)n_total * mn_words(HW) * 4) + (size_t)n_total * (size_t)((n_max + 63) / 64) * 8);
 }
 
 extern "C" int prn_mask_nms(const unsigned char* masks, const int64_t* labels, const float* sum_masks, const int* seg, int n_img, int n_max, int64_t HW, float thr,

@@ -7,33 +7,20 @@
 // reference multiplies the two [n, H*W] float mask matrices; masks are binary, so the intersection of a pair is a population
 // count.  Here every mask is packed to one bit per pixel once (H*W/8 bytes, read back from L2 by every pair) and a pair costs
 // H*W/32 AND+popcount steps -- integer-exact, so the fp32 quotient equals the reference's bit for bit.
-#include "prn_common.h"
+#include "prn_masks.h"
 
 namespace {
-// bit i of word w of mask m = (mask[m][32 w + i] != 0); area[m] += popcount (integer atomics: order-independent)
+// bit i of word w of mask m = (mask[m][32 w + i] != 0) (prn_masks.h); area[m] += popcount (integer atomics: order-independent)
 __global__ __launch_bounds__(256) void mask_pack_kernel(const unsigned char* __restrict__ masks, unsigned* __restrict__ bits, unsigned* __restrict__ area,
                                                         int64_t HW, int words) {
   const int m = blockIdx.y;
   const int w = blockIdx.x * 256 + threadIdx.x;
   unsigned word = 0;
   if (w < words) {
-    const unsigned char* src = masks + (size_t)m * HW + (size_t)w * 32;
-    const int64_t left = HW - (int64_t)w * 32;
-    if (left >= 32 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
-      const uint4 q0 = reinterpret_cast<const uint4*>(src)[0], q1 = reinterpret_cast<const uint4*>(src)[1];
-      const unsigned v[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
-#pragma unroll
-      for (int k = 0; k < 8; ++k)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) word |= ((v[k] >> (8 * b)) & 0xffu) ? (1u << (4 * k + b)) : 0u;
-    } else {
-      for (int i = 0; i < 32 && i < left; ++i) word |= src[i] ? (1u << i) : 0u;
-    }
+    word = prn_mask_bits32(masks + (size_t)m * HW + (size_t)w * 32, HW - (int64_t)w * 32);
     bits[(size_t)m * words + w] = word;
   }
-  int cnt = __popc(word);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+  const int cnt = wave_sum_i(__popc(word));
   if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(area + m, (unsigned)cnt);
 }
 
@@ -50,8 +37,7 @@ __global__ __launch_bounds__(256) void pair_iou_kernel(const unsigned* __restric
     const unsigned* pb = bits_b + (size_t)b * words;
     int cnt = 0;
     for (int w = threadIdx.x; w < words; w += 256) cnt += __popc(pa[w] & pb[w]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    cnt = wave_sum_i(cnt);
     __shared__ int sm[4];
     if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = cnt;
     __syncthreads();
@@ -142,7 +128,6 @@ extern "C" int prn_depth_metrics(const float* pred, const float* gt, double* out
 // ---- pairwise IoU -------------------------------------------------------------------------------------------------
 namespace {
 inline size_t iou_words(int64_t HW) { return (size_t)((HW + 31) / 32); }
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 // Category scores of one grid level for the post-process: sigmoid, then the 2x2 "point NMS" of models/functions/nms.py:8-12 (a cell
 // keeps its score iff it is the maximum of the window {i-1, i} x {j-1, j}), written channels-last into the level's rows of the
 // [B, cells, C] score matrix the candidate selection reads -- sigmoid + max_pool2d + eq + float + mul + permute + cat in one launch.
@@ -273,7 +258,7 @@ __global__ __launch_bounds__(256) void matrix_nms_coef_kernel(const float* __res
 
 extern "C" int64_t prn_pairwise_iou_ws_bytes(int A, int B, int64_t HW) {
   if (A <= 0 || B <= 0 || HW <= 0) return 256;
-  return (int64_t)(align256((size_t)(A + B) * 4) + (size_t)(A + B) * iou_words(HW) * 4);
+  return (int64_t)(prn_align256((size_t)(A + B) * 4) + (size_t)(A + B) * iou_words(HW) * 4);
 }
 
 extern "C" int prn_pairwise_iou(const unsigned char* masks_a, const unsigned char* masks_b, const float* boxes_a, const float* boxes_b, int A, int B,
@@ -289,7 +274,7 @@ extern "C" int prn_pairwise_iou(const unsigned char* masks_a, const unsigned cha
   const int words = (int)iou_words(HW > 0 ? HW : 1);
   if (want_mask) {
     area = (unsigned*)ws;
-    bits = (unsigned*)((char*)ws + align256((size_t)(A + B) * 4));
+    bits = (unsigned*)((char*)ws + prn_align256((size_t)(A + B) * 4));
     PRN_REQUIRE(hipMemsetAsync(area, 0, (size_t)(A + B) * 4, st) == hipSuccess, "prn_pairwise_iou: memset failed");
     hipLaunchKernelGGL(mask_pack_kernel, dim3(cdiv(words, 256), A), dim3(256), 0, st, masks_a, bits, area, HW, words);
     hipLaunchKernelGGL(mask_pack_kernel, dim3(cdiv(words, 256), B), dim3(256), 0, st, masks_b, bits + (size_t)A * words, area + A, HW, words);

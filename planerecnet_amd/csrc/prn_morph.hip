@@ -9,8 +9,7 @@
 //
 // A mask is worked on packed, one bit per pixel, every ROW starting on a 64-bit word (wpr = ceil(W / 64) words per row; bit i of word j of a
 // row is column 64 j + i), so that rows shift independently and the column pass is a word-wise AND.  The square is separable:
-//   pack     one thread per word: 64 mask bytes -> 64 bits (16-byte loads only from 16-byte aligned addresses whose 16 bytes lie inside the
-//            row, single bytes otherwise: an odd H * W puts masks on odd addresses).  Pad bits of a row's last word are 0.
+//   pack     one thread per word: 64 mask bytes -> 64 bits, four groups of 16 inside the row (prn_masks.h).  Pad bits of a row's last word are 0.
 //   row      one thread per word: R[y][x] = AND of the bits x-rx .. x+rx of row y, rx = min(r, W) (a window that long already covers the row
 //            and both borders).  A window AND of length n <= 64 is taken on a 128-bit value by doubling (lengths 1, 2, 4, ... and one
 //            overlapping step to n); a longer one is the AND of such 64-windows, 64 bits apart, plus one that ends at the window's end.  The
@@ -24,7 +23,7 @@
 //            prn_pairwise_iou's kernel.
 // No workgroup waits for another, every loop is bounded by the sizes, the only atomics are integer adds: results are identical run to run and
 // between a batched call and per-image calls.
-#include "prn_common.h"
+#include "prn_masks.h"
 
 namespace {
 
@@ -37,67 +36,28 @@ static_assert(PRN_MORPH_TILE_ROWS == MO_ROWS && PRN_MORPH_TILE_WORDS == MO_COLS 
 static_assert(MO_ROWS * MO_COLS == 256 && (1 << MO_CSHIFT) == MO_COLS, "one thread per word of the tile");
 
 inline int mo_wpr(int W) { return (W + 63) >> 6; }
-inline size_t mo_align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// where the masks come from: the caller's ragged batch, or (flat != NULL) [N][H][W] bytes back to back
-struct mo_src {
-  const unsigned char* const* masks;
-  const int* first;
-  int B;
-  const unsigned char* flat;
-};
-
-__device__ __forceinline__ const unsigned char* mo_mask(const mo_src& s, int n, size_t HW) {
-  if (s.flat) return s.flat + (size_t)n * HW;
-  int lo = 0, hi = s.B - 1;
-  while (lo < hi) {                                                 // the last b with first[b] <= n (empty images are skipped)
-    const int mid = (lo + hi + 1) >> 1;
-    if (s.first[mid] <= n) lo = mid; else hi = mid - 1;
-  }
-  return s.masks[lo] + (size_t)(n - s.first[lo]) * HW;
-}
-
-__device__ __forceinline__ unsigned mo_nz4(unsigned v) {            // one bit per non-zero byte of v (bits 0..3)
-  v |= v >> 4; v |= v >> 2; v |= v >> 1;
-  v &= 0x01010101u;
-  return (v & 1u) | ((v >> 7) & 2u) | ((v >> 14) & 4u) | ((v >> 21) & 8u);
-}
-
-__device__ __forceinline__ int mo_wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // the bits that exist in word j of a row
 __device__ __forceinline__ u64 mo_valid(int j, int wpr, int W) { return (j == wpr - 1 && (W & 63)) ? ((1ull << (W & 63)) - 1ull) : ~0ull; }
 
 // ---- pack ----
-__global__ __launch_bounds__(256) void morph_pack_kernel(mo_src src, int H, int W, int wpr, u64* __restrict__ bits, unsigned* __restrict__ area) {
+__global__ __launch_bounds__(256) void morph_pack_kernel(prn_mask_src src, int H, int W, int wpr, u64* __restrict__ bits, unsigned* __restrict__ area) {
   const int n = blockIdx.y;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;        // word of the mask: y * wpr + j
   u64 word = 0;
   if (i < (int64_t)H * wpr) {
     const int y = (int)(i / wpr), j = (int)(i - (int64_t)y * wpr);
-    const unsigned char* row = mo_mask(src, n, (size_t)H * W) + (size_t)y * W;
+    const unsigned char* row = prn_mask_ptr(src, n, (size_t)H * W) + (size_t)y * W;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const int x = 64 * j + 16 * g;
       if (x >= W) break;
-      const unsigned char* p = row + x;
-      unsigned b16 = 0;
-      if (x + 16 <= W && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-        const uint4 q = *reinterpret_cast<const uint4*>(p);
-        b16 = mo_nz4(q.x) | (mo_nz4(q.y) << 4) | (mo_nz4(q.z) << 8) | (mo_nz4(q.w) << 12);
-      } else {
-        for (int k = 0; k < 16 && x + k < W; ++k) b16 |= p[k] ? (1u << k) : 0u;
-      }
-      word |= (u64)b16 << (16 * g);
+      word |= (u64)prn_mask_bits16(row + x, W - x) << (16 * g);
     }
     bits[(size_t)n * H * wpr + (size_t)i] = word;
   }
   if (area) {                                                       // (uniform: every lane of the wave takes the shuffles)
-    const int cnt = mo_wave_sum(__popcll(word));
+    const int cnt = wave_sum_i(__popcll(word));
     if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(area + n, (unsigned)cnt);
   }
 }
@@ -236,7 +196,7 @@ __global__ __launch_bounds__(256) void morph_col_kernel(const u64* __restrict__ 
     }
   }
   if (area) {
-    cnt = mo_wave_sum(cnt);
+    cnt = wave_sum_i(cnt);
     if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(area + n, cnt);
   }
 }
@@ -254,8 +214,8 @@ __global__ __launch_bounds__(256) void boundary_pair_kernel(const u64* __restric
     cm += __popcll(mask_a[oa + w] & mask_b[ob + w]);
     cb += __popcll(band_a[oa + w] & band_b[ob + w]);
   }
-  cm = mo_wave_sum(cm);
-  cb = mo_wave_sum(cb);
+  cm = wave_sum_i(cm);
+  cb = wave_sum_i(cb);
   __shared__ int sm[2][4];
   if ((threadIdx.x & 63) == 0) { sm[0][threadIdx.x >> 6] = cm; sm[1][threadIdx.x >> 6] = cb; }
   __syncthreads();
@@ -273,7 +233,7 @@ inline bool mo_sizes_ok(int64_t N, int H, int W, int radius) {
 inline size_t mo_words(int H, int W) { return (size_t)H * (size_t)mo_wpr(W); }
 
 // pack, row and column launches over N masks (N <= 65535: the grid's y).  skip: the measurement aid of include/prn.h
-int mo_engine(const char* who, const mo_src& src, int N, int H, int W, int radius, int op, int border, u64* bits, u64* rows, unsigned* mask_area,
+int mo_engine(const char* who, const prn_mask_src& src, int N, int H, int W, int radius, int op, int border, u64* bits, u64* rows, unsigned* mask_area,
               unsigned char* out_bytes, u64* out_bits, int* out_area, hipStream_t st) {
   const int wpr = mo_wpr(W);
   const int64_t words = (int64_t)H * wpr;
@@ -312,13 +272,13 @@ extern "C" int prn_morph(const unsigned char* const* masks_dev, const int* first
   if (area) PRN_REQUIRE(hipMemsetAsync(area, 0, (size_t)Ntot * 4, st) == hipSuccess, "prn_morph: memset failed");
   u64* bits = (u64*)ws;
   u64* rows = bits + (size_t)Ntot * mo_words(H, W);
-  const mo_src src = {masks_dev, first_dev, B, nullptr};
+  const prn_mask_src src = {masks_dev, first_dev, B, nullptr};
   return mo_engine("prn_morph", src, Ntot, H, W, radius, op, op == OP_BOUNDARY ? 0 : border, bits, rows, nullptr, out, nullptr, area, st);
 }
 
 extern "C" int64_t prn_boundary_iou_ws_bytes(int A, int B, int H, int W) {
   if (A <= 0 || B <= 0 || A >= 65536 || B >= 65536 || H <= 0 || W <= 0 || (int64_t)H * W >= (1LL << 24)) return -1;
-  return (int64_t)(mo_align256((size_t)(A + B) * 8) + 3 * (size_t)(A + B) * mo_words(H, W) * 8);
+  return (int64_t)(prn_align256((size_t)(A + B) * 8) + 3 * (size_t)(A + B) * mo_words(H, W) * 8);
 }
 
 extern "C" int prn_boundary_iou(const unsigned char* masks_a, const unsigned char* masks_b, int A, int B, int H, int W, int radius, float* mask_iou,
@@ -332,11 +292,11 @@ extern "C" int prn_boundary_iou(const unsigned char* masks_a, const unsigned cha
   const size_t words = mo_words(H, W), N = (size_t)A + B;
   unsigned* marea = (unsigned*)ws;                                  // [A + B] mask areas, then [A + B] band areas
   unsigned* barea = marea + N;
-  u64* bits = (u64*)((char*)ws + mo_align256(N * 8));
+  u64* bits = (u64*)((char*)ws + prn_align256(N * 8));
   u64* rows = bits + N * words;
   u64* band = rows + N * words;
   PRN_REQUIRE(hipMemsetAsync(marea, 0, N * 8, st) == hipSuccess, "prn_boundary_iou: memset failed");
-  const mo_src sa = {nullptr, nullptr, 0, masks_a}, sb = {nullptr, nullptr, 0, masks_b};
+  const prn_mask_src sa = {nullptr, nullptr, 0, masks_a}, sb = {nullptr, nullptr, 0, masks_b};
   if (int rc = mo_engine("prn_boundary_iou/a", sa, A, H, W, radius, OP_BOUNDARY, 0, bits, rows, marea, nullptr, band, (int*)barea, st)) return rc;
   if (int rc = mo_engine("prn_boundary_iou/b", sb, B, H, W, radius, OP_BOUNDARY, 0, bits + A * words, rows + A * words, marea + A, nullptr, band + A * words,
                          (int*)barea + A, st))

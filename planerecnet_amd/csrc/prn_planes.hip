@@ -3,7 +3,7 @@
 // models/functions/funcs.py:287-291) with a Python loop over the instances: boolean indexing, torch.svd and torch.where per
 // instance, one device -> host round trip each.  Here a whole ragged batch is three launches:
 //   moments  grid (tiles, B): one 1024-pixel tile of one image per workgroup, its four waves take the image's instances round
-//            robin; every mask byte is read once (16 per lane), the depth once per tile.  Per (instance, tile): count, mean and
+//            robin; every mask byte is read once (16 per lane: prn_masks.h), the depth once per tile.  Per (instance, tile): count, mean and
 //            centred scatter in fp64 -- two passes over the lane's 16 points, then Chan's pairwise update across the wave in a
 //            fixed butterfly order.  The same pass writes the owner map (highest covering instance index per pixel).
 //   solve    one wave per instance: the tile partials merged in index order (lane-strided, then the same butterfly), a cyclic
@@ -11,7 +11,7 @@
 //   render   one pixel per lane: the owner's plane evaluated along the pixel's ray, optional (lo, hi) -> NaN epilogue.
 // No atomics on floating-point values and no order that depends on scheduling: results are bit-identical run to run and
 // between a batched call and per-image calls (an instance's partials depend only on its own image and the tile grid).
-#include "prn_common.h"
+#include "prn_masks.h"
 
 namespace {
 
@@ -51,26 +51,6 @@ __device__ __forceinline__ void wave_merge(Mom& m) {
   }
 }
 
-__device__ __forceinline__ unsigned nz4(unsigned v) {               // one bit per non-zero byte of v (bits 0..3)
-  v |= v >> 4; v |= v >> 2; v |= v >> 1;
-  v &= 0x01010101u;
-  return (v & 1u) | ((v >> 7) & 2u) | ((v >> 14) & 4u) | ((v >> 21) & 8u);
-}
-
-// the 16 mask bytes of pixels p0 .. p0+15 of one instance as 16 bits; one 16-byte load where it is aligned and in range
-__device__ __forceinline__ unsigned mask_bits16(const unsigned char* __restrict__ m, int p0, int HW) {
-  const unsigned char* p = m + p0;
-  if (p0 + PL_PX <= HW && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-    const uint4 v = *reinterpret_cast<const uint4*>(p);
-    return nz4(v.x) | (nz4(v.y) << 4) | (nz4(v.z) << 8) | (nz4(v.w) << 12);
-  }
-  unsigned bits = 0;
-#pragma unroll
-  for (int k = 0; k < PL_PX; ++k)
-    if (p0 + k < HW && p[k]) bits |= 1u << k;
-  return bits;
-}
-
 // grid (ntiles, B), 256 threads.  part [Ntot][ntiles][PL_STATS] (an empty pair writes only its count), owner [B][HW].
 __global__ __launch_bounds__(256) void planes_moments_kernel(const float* __restrict__ depth, const unsigned char* const* __restrict__ masks,
                                                              const int* __restrict__ first, const double* __restrict__ K, int W, int HW, int ntiles,
@@ -97,10 +77,10 @@ __global__ __launch_bounds__(256) void planes_moments_kernel(const float* __rest
     Z[k] = z;
     ow[k] = -1;
   }
-  unsigned cur = wave < nb ? mask_bits16(mb + (size_t)wave * HW, p0, HW) : 0u;
+  unsigned cur = wave < nb ? prn_mask_bits16(mb + (size_t)wave * HW + p0, HW - p0) : 0u;
   for (int i = wave; i < nb; i += PL_WAVES) {
     const unsigned bits = cur;
-    cur = i + PL_WAVES < nb ? mask_bits16(mb + (size_t)(i + PL_WAVES) * HW, p0, HW) : 0u;      // next instance's bytes in flight
+    cur = i + PL_WAVES < nb ? prn_mask_bits16(mb + (size_t)(i + PL_WAVES) * HW + p0, HW - p0) : 0u;      // next instance's bytes in flight
     double* dst = part + ((size_t)(i0 + i) * ntiles + tile) * PL_STATS;
     if (!__any(bits != 0u)) {                                     // wave-uniform: nothing of this instance in the tile
       if (lane == 0) dst[0] = 0.0;
@@ -251,7 +231,8 @@ __global__ __launch_bounds__(256) void planes_render_kernel(const float* __restr
   out[g] = z;
 }
 
-constexpr int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
+// ws = the per-(instance, tile) partials | the owner map (sizes_ok: positive and far below 2^63)
+inline int64_t pl_part_bytes(int64_t Ntot, int64_t ntiles) { return (int64_t)prn_align256((size_t)(Ntot * ntiles * PL_STATS) * sizeof(double)); }
 
 bool sizes_ok(int B, int Ntot, int H, int W) {
   return B > 0 && B < 65536 && Ntot >= 0 && H > 0 && W > 0 && (int64_t)H * W < (1LL << 31) && (int64_t)B * H * W < (1LL << 40) &&
@@ -263,7 +244,7 @@ bool sizes_ok(int B, int Ntot, int H, int W) {
 extern "C" int64_t prn_planes_ws_bytes(int B, int Ntot, int H, int W) {
   if (!sizes_ok(B, Ntot, H, W)) return -1;
   const int64_t HW = (int64_t)H * W, ntiles = cdiv(HW, PL_TILE);
-  return align256((int64_t)Ntot * ntiles * PL_STATS * (int64_t)sizeof(double)) + align256((int64_t)B * HW * (int64_t)sizeof(int));
+  return pl_part_bytes(Ntot, ntiles) + (int64_t)prn_align256((size_t)B * HW * sizeof(int));
 }
 
 extern "C" int prn_planes_fit(const float* depth, const unsigned char* const* masks_dev, const int* first_dev, const double* k_dev, int B, int Ntot,
@@ -274,7 +255,7 @@ extern "C" int prn_planes_fit(const float* depth, const unsigned char* const* ma
   PRN_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "prn_planes_fit: workspace must be 16-byte aligned");
   const int HW = H * W, ntiles = cdiv(HW, PL_TILE);
   double* part = static_cast<double*>(ws);
-  int* owner = reinterpret_cast<int*>(static_cast<char*>(ws) + align256((int64_t)Ntot * ntiles * PL_STATS * (int64_t)sizeof(double)));
+  int* owner = reinterpret_cast<int*>(static_cast<char*>(ws) + pl_part_bytes(Ntot, ntiles));
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(planes_moments_kernel, dim3(ntiles, B), dim3(256), 0, st, depth, masks_dev, first_dev, k_dev, W, HW, ntiles, part, owner);
   PRN_CHECK_LAUNCH("prn_planes_fit/moments");
@@ -295,7 +276,7 @@ extern "C" int prn_planes_render(const float* depth, const unsigned char* const*
   PRN_REQUIRE(!has_range || lo < hi, "prn_planes_render: empty depth range (lo=%g hi=%g)", (double)lo, (double)hi);
   PRN_REQUIRE(out != depth, "prn_planes_render: the output must not alias the input depth");
   const int HW = H * W, ntiles = cdiv(HW, PL_TILE);
-  const int* owner = reinterpret_cast<const int*>(static_cast<const char*>(ws) + align256((int64_t)Ntot * ntiles * PL_STATS * (int64_t)sizeof(double)));
+  const int* owner = reinterpret_cast<const int*>(static_cast<const char*>(ws) + pl_part_bytes(Ntot, ntiles));
   hipLaunchKernelGGL(planes_render_kernel, dim3(cdiv(HW, 256), B), dim3(256), 0, (hipStream_t)stream, depth, masks_dev, first_dev, k_dev, planes, valid,
                      owner, W, HW, has_range, lo, hi, out);
   PRN_CHECK_LAUNCH("prn_planes_render");

@@ -11,7 +11,7 @@
 //   colours   one pass, four pixels per thread.
 // A scalar path (bytes / single floats, bounds checked per pixel) covers widths that are no multiple of four and unaligned pointers; it
 // runs the same arithmetic per pixel and writes the same bytes.
-#include "prn_common.h"
+#include "prn_masks.h"
 
 namespace {
 
@@ -20,12 +20,6 @@ constexpr int RD_TAB = 128;                    // instances per chunk of the box
 constexpr int RD_G = 16;                       // instances whose mask words are fetched together
 constexpr int RD_LW = RD_TW / 4 + 2;           // outline mode: words of a staged row (one halo word on each side)
 constexpr int RD_LH = RD_TH + 2;               //               rows of a staged tile (one halo row above and below)
-
-__device__ __forceinline__ unsigned nz4(unsigned v) {               // one bit per non-zero byte of v (bits 0..3)
-  v |= v >> 4; v |= v >> 2; v |= v >> 1;
-  v &= 0x01010101u;
-  return (v & 1u) | ((v >> 7) & 2u) | ((v >> 14) & 4u) | ((v >> 21) & 8u);
-}
 
 // the mask bytes of pixels (y, x .. x+3) of one instance as a word, x a multiple of 4 (-4 and >= W occur in the halo); outside the image: 0
 template <bool WIDE>
@@ -119,9 +113,9 @@ __global__ __launch_bounds__(256) void render_overlay_kernel(const float* __rest
           const int j = jt - g;
           if (j < 0) break;
           const unsigned* t = s_m + g * (RD_LH * RD_LW) + (ty + 1) * RD_LW + tx + 1;
-          const unsigned C = nz4(t[0]);
+          const unsigned C = prn_nz4(t[0]);
           if (C == 0u) continue;
-          const unsigned U = nz4(t[-RD_LW]), D = nz4(t[RD_LW]);
+          const unsigned U = prn_nz4(t[-RD_LW]), D = prn_nz4(t[RD_LW]);
           const unsigned L = ((C << 1) & 15u) | (t[-1] >> 24 ? 1u : 0u), R = (C >> 1) | (t[1] & 255u ? 8u : 0u);
           cont |= C & ~(U & D & L & R);                           // set, and a 4-neighbour is not (outside the image counts as not set)
           if (do_mask) blend4(v, C, s_ca[j], oma);
@@ -135,7 +129,7 @@ __global__ __launch_bounds__(256) void render_overlay_kernel(const float* __rest
         for (int g = 0; g < RD_G; ++g) w[g] = (live && jt - g >= 0) ? mask_word<WIDE>(mp + (size_t)(jt - g) * HW, y, x, H, W) : 0u;
 #pragma unroll
         for (int g = 0; g < RD_G; ++g)
-          if (w[g] != 0u) blend4(v, nz4(w[g]), s_ca[jt - g], oma);
+          if (w[g] != 0u) blend4(v, prn_nz4(w[g]), s_ca[jt - g], oma);
       }
     }
 

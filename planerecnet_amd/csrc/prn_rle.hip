@@ -2,7 +2,7 @@
 // its runs are what every COCO tool exchanges, as a delta-coded string of 6-bit characters.  The masks are N H W bytes in HBM and their strings a few
 // kilobytes, so the coding runs where the masks are and only the strings travel.
 //   encode  A run boundary sits at p exactly when m[y][x] differs from its column-major predecessor (m[y-1][x]; m[H-1][x-1] for y = 0; 0 for p = 0).
-//           Boundaries are found row-major: adjacent lanes on adjacent columns (four columns per lane through one 4-byte load where W % 4 == 0),
+//           Boundaries are found row-major: adjacent lanes on adjacent columns (four columns per lane where W % 4 == 0; prn_masks.h reads them),
 //           every lane walking down a segment of RLE_SEG rows with the pixel above carried in a register.  Only the RANK of a boundary needs the
 //           column-major order; it comes from per-(mask, column, row segment) counts (launch 1) and an exclusive scan over them in (column,
 //           segment) order (launch 2, one workgroup per mask).  Launch 3 repeats the walk and writes every boundary position at its rank.
@@ -11,7 +11,7 @@
 //           the characters.  Nothing is ordered by an atomic: there is none in this file.
 //   decode  prn_rle_paint: out[n][y][x] = (number of run ends <= x * H + y) & 1.  A 128 x 8 tile needs only the ends between its lowest and
 //           highest position; they are staged in LDS when they fit and searched there (binary search), else searched in place.
-#include "prn_common.h"
+#include "prn_masks.h"
 
 namespace {
 
@@ -20,45 +20,25 @@ constexpr int RLE_LX = 64, RLE_LY = 4;         // lanes of a workgroup across co
 constexpr int RLE_PW = 128, RLE_PH = 8;        // paint: pixels of one workgroup (32 lanes x 4 pixels wide, 8 rows)
 constexpr int RLE_STAGE = 2048;                // paint: run ends of a tile that fit its LDS
 
-__device__ __forceinline__ unsigned nz4(unsigned v) {               // one bit per non-zero byte of v (bits 0..3)
-  v |= v >> 4; v |= v >> 2; v |= v >> 1;
-  v &= 0x01010101u;
-  return (v & 1u) | ((v >> 7) & 2u) | ((v >> 14) & 4u) | ((v >> 21) & 8u);
-}
-
-// image and local index of global instance n (first[b] <= n < first[b+1]; empty images are skipped)
-__device__ __forceinline__ const unsigned char* mask_of(const unsigned char* const* __restrict__ masks, const int* __restrict__ first, int B, int n,
-                                                        size_t HW) {
-  int lo = 0, hi = B - 1;
-  while (lo < hi) {                                                 // the last b with first[b] <= n
-    const int mid = (lo + hi + 1) >> 1;
-    if (first[mid] <= n) lo = mid; else hi = mid - 1;
-  }
-  return masks[lo] + (size_t)(n - first[lo]) * HW;
-}
-
 // set bits of pixels (y, x .. x+CPL-1), bit k = column x + k; CPL == 4: x % 4 == 0 and the row holds all four
 template <int CPL>
-__device__ __forceinline__ unsigned row_bits(const unsigned char* __restrict__ m, int y, int x, int W, bool word) {
-  const unsigned char* p = m + (size_t)y * W + x;
-  if (CPL == 1) return p[0] ? 1u : 0u;
-  if (word) return nz4(*reinterpret_cast<const unsigned*>(p));
-  return (p[0] ? 1u : 0u) | (p[1] ? 2u : 0u) | (p[2] ? 4u : 0u) | (p[3] ? 8u : 0u);
+__device__ __forceinline__ unsigned row_bits(const unsigned char* __restrict__ m, int y, int x, int W) {
+  return prn_mask_bits4(m + (size_t)y * W + x, CPL);
 }
 
 // The walk both encoder launches share: rows y0 .. y1-1 of columns x .. x+CPL-1, f(k, y) for every boundary at (y, x + k), top to bottom.
 template <int CPL, class F>
-__device__ __forceinline__ void rle_walk(const unsigned char* __restrict__ m, int H, int W, int x, int y0, int y1, bool word, F&& f) {
+__device__ __forceinline__ void rle_walk(const unsigned char* __restrict__ m, int H, int W, int x, int y0, int y1, F&& f) {
   unsigned prev;
   if (y0 > 0) {
-    prev = row_bits<CPL>(m, y0 - 1, x, W, word);
+    prev = row_bits<CPL>(m, y0 - 1, x, W);
   } else {                                                          // the predecessor of (0, x) is (H-1, x-1); of p = 0: a zero
     const unsigned left = x > 0 ? (m[(size_t)(H - 1) * W + x - 1] ? 1u : 0u) : 0u;
-    prev = CPL == 1 ? left : (((row_bits<CPL>(m, H - 1, x, W, word) << 1) & 15u) | left);
+    prev = CPL == 1 ? left : (((row_bits<CPL>(m, H - 1, x, W) << 1) & 15u) | left);
   }
 #pragma unroll 4
   for (int y = y0; y < y1; ++y) {
-    const unsigned cur = row_bits<CPL>(m, y, x, W, word);
+    const unsigned cur = row_bits<CPL>(m, y, x, W);
     const unsigned d = cur ^ prev;
     prev = cur;
     if (d) {
@@ -80,17 +60,16 @@ __device__ __forceinline__ bool rle_place(int W, int nseg, int colblocks, int& n
 
 // launch 1: cells[n][x * nseg + s] = boundaries of column x inside row segment s
 template <int CPL>
-__global__ __launch_bounds__(RLE_LX* RLE_LY) void rle_count_kernel(const unsigned char* const* __restrict__ masks, const int* __restrict__ first, int B, int H,
-                                                                   int W, int nseg, int colblocks, unsigned* __restrict__ cells) {
+__global__ __launch_bounds__(RLE_LX* RLE_LY) void rle_count_kernel(prn_mask_src src, int H, int W, int nseg, int colblocks,
+                                                                   unsigned* __restrict__ cells) {
   int n, x, s;
   if (!rle_place<CPL>(W, nseg, colblocks, n, x, s)) return;
-  const unsigned char* m = mask_of(masks, first, B, n, (size_t)H * W);
-  const bool word = CPL == 4 && ((uintptr_t)m & 3u) == 0;
+  const unsigned char* m = prn_mask_ptr(src, n, (size_t)H * W);
   unsigned c[CPL];
 #pragma unroll
   for (int k = 0; k < CPL; ++k) c[k] = 0u;
   const int y0 = s * RLE_SEG, y1 = min(H, y0 + RLE_SEG);
-  rle_walk<CPL>(m, H, W, x, y0, y1, word, [&](int k, int) { ++c[k]; });
+  rle_walk<CPL>(m, H, W, x, y0, y1, [&](int k, int) { ++c[k]; });
   unsigned* o = cells + (size_t)n * W * nseg + (size_t)x * nseg + s;
 #pragma unroll
   for (int k = 0; k < CPL; ++k) o[(size_t)k * nseg] = c[k];
@@ -137,13 +116,12 @@ __global__ __launch_bounds__(256) void rle_scan_kernel(unsigned* __restrict__ ce
 
 // launch 3: the walk again, every boundary position to pos[pos_first[n] + rank]
 template <int CPL>
-__global__ __launch_bounds__(RLE_LX* RLE_LY) void rle_fill_kernel(const unsigned char* const* __restrict__ masks, const int* __restrict__ first, int B, int H,
-                                                                  int W, int nseg, int colblocks, const unsigned* __restrict__ cells,
-                                                                  const int64_t* __restrict__ pos_first, unsigned* __restrict__ pos) {
+__global__ __launch_bounds__(RLE_LX* RLE_LY) void rle_fill_kernel(prn_mask_src src, int H, int W, int nseg, int colblocks,
+                                                                  const unsigned* __restrict__ cells, const int64_t* __restrict__ pos_first,
+                                                                  unsigned* __restrict__ pos) {
   int n, x, s;
   if (!rle_place<CPL>(W, nseg, colblocks, n, x, s)) return;
-  const unsigned char* m = mask_of(masks, first, B, n, (size_t)H * W);
-  const bool word = CPL == 4 && ((uintptr_t)m & 3u) == 0;
+  const unsigned char* m = prn_mask_ptr(src, n, (size_t)H * W);
   const unsigned* o = cells + (size_t)n * W * nseg + (size_t)x * nseg + s;
   const int64_t p0 = pos_first[n];
   const unsigned room = (unsigned)(pos_first[n + 1] - p0);          // a rank past the mask's own slots is never stored
@@ -151,7 +129,7 @@ __global__ __launch_bounds__(RLE_LX* RLE_LY) void rle_fill_kernel(const unsigned
 #pragma unroll
   for (int k = 0; k < CPL; ++k) r[k] = o[(size_t)k * nseg];
   const int y0 = s * RLE_SEG, y1 = min(H, y0 + RLE_SEG);
-  rle_walk<CPL>(m, H, W, x, y0, y1, word, [&](int k, int y) {
+  rle_walk<CPL>(m, H, W, x, y0, y1, [&](int k, int y) {
     const unsigned rank = r[k]++;
     if (rank < room) pos[p0 + rank] = (unsigned)(x + k) * (unsigned)H + (unsigned)y;
   });
@@ -287,8 +265,9 @@ int prn_rle_count(const unsigned char* const* masks_dev, const int* first_dev, i
   hipStream_t st = (hipStream_t)stream;
   unsigned* cells = (unsigned*)ws;
   const dim3 blk(RLE_LX, RLE_LY);
-  if (g.cpl == 4) rle_count_kernel<4><<<g.grid, blk, 0, st>>>(masks_dev, first_dev, B, H, W, g.nseg, g.colblocks, cells);
-  else rle_count_kernel<1><<<g.grid, blk, 0, st>>>(masks_dev, first_dev, B, H, W, g.nseg, g.colblocks, cells);
+  const prn_mask_src src = {masks_dev, first_dev, B, nullptr};
+  if (g.cpl == 4) rle_count_kernel<4><<<g.grid, blk, 0, st>>>(src, H, W, g.nseg, g.colblocks, cells);
+  else rle_count_kernel<1><<<g.grid, blk, 0, st>>>(src, H, W, g.nseg, g.colblocks, cells);
   PRN_CHECK_LAUNCH("prn_rle_count (count)");
   rle_scan_kernel<<<Ntot, 256, 0, st>>>(cells, W * g.nseg, totals);
   PRN_CHECK_LAUNCH("prn_rle_count (scan)");
@@ -302,8 +281,9 @@ int prn_rle_fill(const unsigned char* const* masks_dev, const int* first_dev, in
   PRN_REQUIRE(B > 0 && masks_dev && first_dev && ws && pos_first && pos, "prn_rle_fill: null argument or B=%d", B);
   hipStream_t st = (hipStream_t)stream;
   const dim3 blk(RLE_LX, RLE_LY);
-  if (g.cpl == 4) rle_fill_kernel<4><<<g.grid, blk, 0, st>>>(masks_dev, first_dev, B, H, W, g.nseg, g.colblocks, (const unsigned*)ws, pos_first, pos);
-  else rle_fill_kernel<1><<<g.grid, blk, 0, st>>>(masks_dev, first_dev, B, H, W, g.nseg, g.colblocks, (const unsigned*)ws, pos_first, pos);
+  const prn_mask_src src = {masks_dev, first_dev, B, nullptr};
+  if (g.cpl == 4) rle_fill_kernel<4><<<g.grid, blk, 0, st>>>(src, H, W, g.nseg, g.colblocks, (const unsigned*)ws, pos_first, pos);
+  else rle_fill_kernel<1><<<g.grid, blk, 0, st>>>(src, H, W, g.nseg, g.colblocks, (const unsigned*)ws, pos_first, pos);
   PRN_CHECK_LAUNCH("prn_rle_fill");
   return 0;
 }

@@ -11,17 +11,13 @@
 // raster order -- what np.flatnonzero(mask)[r] is on the host) to its pixel by a binary search over the prefix and a scan of one
 // 64-byte segment.  Ranks are either injected (the reference's numpy stream drawn on the host: bit-identical triplets, used by the
 // parity tests) or drawn here by a counter-based generator (Philox4x32-10 keyed by (seed, sample index): production).
-#include "prn_common.h"
+#include "prn_masks.h"
 
 namespace {
 
 constexpr int SEG = 64;                       // pixels per segment
 
 __device__ __forceinline__ uint4 load16(const unsigned char* p) { return *reinterpret_cast<const uint4*>(p); }
-__device__ __forceinline__ unsigned nz_bytes(unsigned v) {          // 0x01 in every byte of v that is non-zero
-  v |= v >> 4; v |= v >> 2; v |= v >> 1;
-  return v & 0x01010101u;
-}
 
 // bit k of the result = pixel k of the 64-pixel segment `s` of region `r` is set
 __device__ __forceinline__ unsigned long long segment_bits(const unsigned char* __restrict__ masks, const int* __restrict__ img_first, int Ntot, int r, int s,
@@ -34,11 +30,7 @@ __device__ __forceinline__ unsigned long long segment_bits(const unsigned char* 
       const uint4 v = load16(base + q * 16);
       const unsigned w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const unsigned n = nz_bytes(w[j]);                      // bytes -> bits 0, 8, 16, 24
-        const unsigned four = (n & 1u) | ((n >> 7) & 2u) | ((n >> 14) & 4u) | ((n >> 21) & 8u);
-        b |= (unsigned long long)four << (q * 16 + j * 4);
-      }
+      for (int j = 0; j < 4; ++j) b |= (unsigned long long)prn_nz4(w[j]) << (q * 16 + j * 4);
     }
     return b;
   };

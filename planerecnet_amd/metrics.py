@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from ._lib import check, lib
+from ._masks import _p, _stream
 from .config import cfg
 
 
@@ -28,9 +29,8 @@ def compute_depth_metrics(pred_depth, gt_depth, median_scaling=True):
         raise RuntimeError("compute_depth_metrics: prediction %s and ground truth %s differ in size" % (tuple(pred.shape), tuple(gt.shape)))
     out = torch.empty(8, device=pred.device, dtype=torch.float64)
     ws = torch.empty(lib.prn_depth_metrics_ws_doubles(), device=pred.device, dtype=torch.float64)
-    stream = ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(pred.device.index))
-    check(lib.prn_depth_metrics(ctypes.c_void_p(pred.data_ptr()), ctypes.c_void_p(gt.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                                ctypes.c_void_p(ws.data_ptr()), pred.numel(), float(cfg.dataset.min_depth), float(cfg.dataset.max_depth), stream),
+    stream = _stream(pred.device)
+    check(lib.prn_depth_metrics(_p(pred), _p(gt), _p(out), _p(ws), pred.numel(), float(cfg.dataset.min_depth), float(cfg.dataset.max_depth), stream),
           "prn_depth_metrics")
     if median_scaling:
         valid = (gt.flatten() > 0.5).logical_and(pred.flatten() > 0.5)
@@ -76,9 +76,8 @@ def pairwise_iou(masks_a=None, masks_b=None, boxes_a=None, boxes_b=None):
     if want_b:
         ba, bb = boxes_a.to(dev).float().contiguous(), boxes_b.to(dev).float().contiguous()
         biou = torch.empty(A, B, device=dev)
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)      # noqa: E731
-    stream = ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index))
-    check(lib.prn_pairwise_iou(ptr(ma), ptr(mb), ptr(ba), ptr(bb), A, B, HW, ptr(miou), ptr(biou), ptr(ws), stream), "prn_pairwise_iou")
+    stream = _stream(dev)
+    check(lib.prn_pairwise_iou(_p(ma), _p(mb), _p(ba), _p(bb), A, B, HW, _p(miou), _p(biou), _p(ws), stream), "prn_pairwise_iou")
     return miou, biou
 
 
@@ -104,9 +103,8 @@ def boundary_iou(masks_a, masks_b, radius=None, ratio=0.02):
     mb = (masks_b if masks_b.dtype in (torch.uint8, torch.bool) else masks_b != 0).to(dev).contiguous().view(torch.uint8)
     out = torch.empty(2, A, B, device=dev)
     ws = torch.empty((nbytes + 7) // 8 * 2, device=dev, dtype=torch.int32)
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
-    stream = ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index))
-    check(lib.prn_boundary_iou(ptr(ma), ptr(mb), A, B, H, W, radius, ptr(out[0]), ptr(out[1]), ptr(ws), stream), "prn_boundary_iou")
+    stream = _stream(dev)
+    check(lib.prn_boundary_iou(_p(ma), _p(mb), A, B, H, W, radius, _p(out[0]), _p(out[1]), _p(ws), stream), "prn_boundary_iou")
     return out[0], out[1]
 
 
@@ -116,14 +114,14 @@ def category_scores(cate_logits):
     B, C = cate_logits[0].shape[:2]
     cells = sum(int(c.shape[2]) * int(c.shape[3]) for c in cate_logits)
     out = torch.empty(B, cells, C, device=cate_logits[0].device, dtype=torch.float32)
-    stream = ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(out.device.index))
+    stream = _stream(out.device)
     off = 0
     for c in cate_logits:
         S = int(c.shape[2])
         if not c.is_cuda or c.dtype != torch.float32 or c.shape[3] != S or c.shape[:2] != (B, C):
             raise RuntimeError("category_scores needs square fp32 device maps of one batch / class count")
         c = c.detach().contiguous()
-        check(lib.prn_sigmoid_point_nms(ctypes.c_void_p(c.data_ptr()), ctypes.c_void_p(out.data_ptr() + 4 * off * C), B, C, S, cells * C, stream), "prn_sigmoid_point_nms")
+        check(lib.prn_sigmoid_point_nms(_p(c), ctypes.c_void_p(out.data_ptr() + 4 * off * C), B, C, S, cells * C, stream), "prn_sigmoid_point_nms")
         off += S * S
     return out
 
@@ -136,9 +134,8 @@ def mask_stats(seg, thr):
     out = torch.empty(2, n, device=seg.device, dtype=torch.float32)
     if n:
         seg = seg.contiguous()
-        stream = ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(seg.device.index))
-        check(lib.prn_mask_stats(ctypes.c_void_p(seg.data_ptr()), n, int(seg[0].numel()), float(thr), ctypes.c_void_p(out[0].data_ptr()),
-                                 ctypes.c_void_p(out[1].data_ptr()), stream), "prn_mask_stats")
+        stream = _stream(seg.device)
+        check(lib.prn_mask_stats(_p(seg), n, int(seg[0].numel()), float(thr), _p(out[0]), _p(out[1]), stream), "prn_mask_stats")
     return out[0], out[1]
 
 
@@ -151,8 +148,8 @@ def mask_boxes(masks):
     out = torch.empty(n, 4, device=masks.device, dtype=torch.float32)
     if n:
         m = masks.contiguous().view(torch.uint8)
-        stream = ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(masks.device.index))
-        check(lib.prn_mask_boxes(ctypes.c_void_p(m.data_ptr()), n, H, W, ctypes.c_void_p(out.data_ptr()), stream), "prn_mask_boxes")
+        stream = _stream(masks.device)
+        check(lib.prn_mask_boxes(_p(m), n, H, W, _p(out), stream), "prn_mask_boxes")
     return out
 
 
@@ -161,9 +158,8 @@ def matrix_nms_scores(iou, labels, scores, sigma, gaussian):
     n = scores.shape[0]
     iou, labels, scores = iou.contiguous(), labels.contiguous().long(), scores.contiguous().float()
     out = torch.empty(2, n, device=scores.device, dtype=torch.float32)          # decayed scores | workspace (per-column denominators)
-    stream = ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(scores.device.index))
-    check(lib.prn_matrix_nms(ctypes.c_void_p(iou.data_ptr()), ctypes.c_void_p(labels.data_ptr()), ctypes.c_void_p(scores.data_ptr()), n, float(sigma),
-                             int(bool(gaussian)), ctypes.c_void_p(out[0].data_ptr()), ctypes.c_void_p(out[1].data_ptr()), stream), "prn_matrix_nms")
+    stream = _stream(scores.device)
+    check(lib.prn_matrix_nms(_p(iou), _p(labels), _p(scores), n, float(sigma), int(bool(gaussian)), _p(out[0]), _p(out[1]), stream), "prn_matrix_nms")
     return out[0]
 
 

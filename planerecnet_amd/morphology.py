@@ -22,7 +22,7 @@ import math
 import numpy as np
 import torch
 
-from .components import MAX_MASKS, _as_bytes, _bytes_buffer, _inputs, _p, _split, _upload
+from ._masks import _as_bytes, _bytes_buffer, _inputs, _p, _split, _stream, ragged_chunks
 
 __all__ = ["erode", "dilate", "boundary", "boundary_radius", "TILE_ROWS", "TILE_WORDS", "LDS_RADIUS"]
 
@@ -82,34 +82,18 @@ def _morph_np(m, op, radius, border):
 # ---- device path -----------------------------------------------------------------------------------------------------------------
 
 def _device_run(parts, op, radius, border, out, area, max_workspace_bytes, what):
-    """parts: contiguous uint8 [N_b,H,W] device tensors with N_b > 0, walked in chunks whose workspace stays under the limit (sizes are
-    host knowledge: nothing is read back); a chunk may span images and an image several chunks."""
+    """parts: contiguous uint8 [N_b,H,W] device tensors with N_b > 0, walked in chunks whose workspace stays under the limit"""
     from ._lib import check, lib
     dev = parts[0].device
     H, W = int(parts[0].shape[1]), int(parts[0].shape[2])
-    HW = H * W
     per_mask = lib.prn_morph_ws_bytes(1, H, W, radius)
     if per_mask < 0:
         raise RuntimeError("%s: H * W must be below 2^31, got %d x %d" % (what, H, W))
-    cap = int(max(1, min(MAX_MASKS, int(max_workspace_bytes) // per_mask)))
-    first = [0]
-    for m in parts:
-        first.append(first[-1] + int(m.shape[0]))
-    stream = ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index))
-    for g0 in range(0, first[-1], cap):
-        g1 = min(first[-1], g0 + cap)
-        ptrs, cnt = [], [0]
-        for b, m in enumerate(parts):
-            lo, hi = max(g0, first[b]), min(g1, first[b + 1])
-            if lo < hi:
-                ptrs.append(m.data_ptr() + (lo - first[b]) * HW)
-                cnt.append(cnt[-1] + hi - lo)
-        n = g1 - g0
-        ws = torch.empty((lib.prn_morph_ws_bytes(n, H, W, radius) + 7) // 8 * 2, dtype=torch.int32, device=dev)
-        ptrs_dev, first_dev = _upload(ptrs, torch.int64, dev), _upload(cnt, torch.int32, dev)
-        check(lib.prn_morph(_p(ptrs_dev), _p(first_dev), len(ptrs), n, H, W, op, radius, border, ctypes.c_void_p(out.data_ptr() + g0 * HW),
-                            ctypes.c_void_p(area.data_ptr() + 4 * g0), _p(ws), stream), "prn_morph")
-        del ptrs_dev, first_dev, ws                                  # (stream-ordered allocator: reuse after this point is ordered behind the launches)
+    for g0, g1, ptrs, first in ragged_chunks(parts, per_mask, max_workspace_bytes):
+        ws = torch.empty((lib.prn_morph_ws_bytes(g1 - g0, H, W, radius) + 7) // 8 * 2, dtype=torch.int32, device=dev)
+        check(lib.prn_morph(_p(ptrs), _p(first), ptrs.numel(), g1 - g0, H, W, op, radius, border, ctypes.c_void_p(out.data_ptr() + g0 * H * W),
+                            ctypes.c_void_p(area.data_ptr() + 4 * g0), _p(ws), _stream(dev)), "prn_morph")
+        del ptrs, first, ws                                          # (stream-ordered allocator: reuse after this point is ordered behind the launches)
 
 
 @torch.no_grad()

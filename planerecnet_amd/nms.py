@@ -48,8 +48,8 @@ def mask_nms_batched(cate_labels, seg_masks, sum_masks, counts, nms_thr=0.5):
     seg_masks [N,h,w] (bool / uint8; another dtype counts as != 0), sum_masks [N]: device tensors, the candidates of image b contiguous and in
     descending score order; counts: host ints per image (zeros allowed, sum N).  -> keep [N] in seg_masks.dtype.  One small upload (the segment
     offsets, through page-locked memory), one workspace, three launches, no host synchronisation."""
-    import ctypes
     from ._lib import check, lib
+    from ._masks import _p as p, _stream, _upload
     if not (seg_masks.is_cuda and cate_labels.is_cuda and sum_masks.is_cuda):
         raise RuntimeError("mask_nms_batched needs device tensors (CPU tensors: mask_nms)")
     counts = [int(c) for c in counts]
@@ -70,10 +70,9 @@ def mask_nms_batched(cate_labels, seg_masks, sum_masks, counts, nms_thr=0.5):
     offsets = [0]
     for c in counts:
         offsets.append(offsets[-1] + c)
-    seg = torch.tensor(offsets, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+    seg = _upload(offsets, torch.int32, dev)
     ws = torch.empty((lib.prn_mask_nms_ws_bytes(N, n_max, HW) + 7) // 8 * 2, device=dev, dtype=torch.float32)
-    p = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
-    stream = ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index))
+    stream = _stream(dev)
     check(lib.prn_mask_nms(p(masks), p(labels), p(sums), p(seg), len(counts), n_max, HW, float(nms_thr), p(keep), p(ws), stream), "prn_mask_nms")
     return keep.to(seg_masks.dtype)
 

@@ -11,22 +11,12 @@ Deviations where the reference crashes or returns an arbitrary plane: an instanc
 below it, or keep the predicted depth).  The reference raises on a 1-pixel mask (`squeeze` turns the [1,3] point set into a
 vector) and returns an arbitrary plane for 2 pixels.
 """
-import ctypes
-
 import torch
 
 from ._lib import check, lib
+from ._masks import _as_bytes, _describe, _p, _stream, _upload
 
 __all__ = ["fit_planes", "planar_depth"]
-
-
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _upload(values, dtype, device):
-    """host values -> device tensor through page-locked memory (an asynchronous copy: no host synchronisation)"""
-    return torch.tensor(values, dtype=dtype).pin_memory().to(device, non_blocking=True)
 
 
 def _intrinsics(k_matrix, B, device):
@@ -46,8 +36,7 @@ class _Fit:
 
     def __init__(self, depth, masks, k_matrix):
         if not (torch.is_tensor(depth) and depth.is_cuda and depth.dtype == torch.float32 and depth.dim() == 4 and depth.shape[1] == 1):
-            got = "%s %s %s" % (depth.device, depth.dtype, tuple(depth.shape)) if torch.is_tensor(depth) else type(depth).__name__
-            raise RuntimeError("depth must be a [B,1,H,W] fp32 device tensor, got %s" % got)
+            raise RuntimeError("depth must be a [B,1,H,W] fp32 device tensor, got %s" % _describe(depth))
         B, _, H, W = depth.shape
         dev = depth.device
         if len(masks) != B:
@@ -58,8 +47,7 @@ class _Fit:
                 m = torch.zeros(0, H, W, dtype=torch.uint8, device=dev)
             if not (m.device == dev and m.dtype in (torch.bool, torch.uint8) and m.dim() == 3 and tuple(m.shape[1:]) == (H, W)):
                 raise RuntimeError("masks[%d] must be a bool / uint8 [N,%d,%d] tensor on %s, got %s %s %s" % (b, H, W, dev, m.device, m.dtype, tuple(m.shape)))
-            m = m.contiguous()
-            ms.append(m.view(torch.uint8) if m.dtype == torch.bool else m)
+            ms.append(_as_bytes(m))
         self.sizes = [int(m.shape[0]) for m in ms]
         first = [0]
         for n in self.sizes:
@@ -78,7 +66,7 @@ class _Fit:
         self.centroid = torch.empty(self.Ntot, 3, dtype=torch.float64, device=dev)
         self.valid = torch.empty(self.Ntot, dtype=torch.bool, device=dev)
         self.count = torch.empty(self.Ntot, dtype=torch.int64, device=dev)
-        self.stream = ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index))
+        self.stream = _stream(dev)
         check(lib.prn_planes_fit(_p(self.depth), _p(self.ptrs), _p(self.first), _p(self.k), B, self.Ntot, H, W, _p(self.planes), _p(self.centroid),
                                  _p(self.valid), _p(self.count), _p(self.ws), self.stream), "prn_planes_fit")
 

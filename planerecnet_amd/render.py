@@ -14,12 +14,11 @@ outlines (Pillow's `rectangle(outline, width=1)`), the 256 colour levels.  Devia
     its documentation goes; OpenCV is not a dependency of this build, so the rule is NOT pinned on OpenCV's output.
   * out-of-range frame values saturate to [0, 255] (numpy's cast wraps); frames from `frame_to_input` are inside the range.
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from ._lib import check, lib
+from ._masks import _as_bytes, _describe, _p, _stream, _upload
 from .config import COLORS
 
 __all__ = ["render_overlay", "depth_limits", "colorize_depth", "viridis_table", "LAYER_MASKS", "LAYER_CONTOURS", "LAYER_BOXES"]
@@ -29,23 +28,6 @@ _BOX_LIMIT = 1 << 30                                         # boxes further out
 _VIRIDIS_STOPS = [0, 64, 128, 192, 255]
 _VIRIDIS_RGB = ([68, 59, 33, 94, 253], [1, 82, 145, 201, 231], [84, 139, 140, 98, 37])
 _TABLES = {}                                                 # device -> the viridis table there (BGR)
-
-
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _upload(values, dtype, device):
-    """host values -> device tensor through page-locked memory (an asynchronous copy: no host synchronisation)"""
-    return torch.tensor(values, dtype=dtype).pin_memory().to(device, non_blocking=True)
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(device.index))
-
-
-def _describe(t):
-    return "%s %s %s" % (t.device, t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__
 
 
 def viridis_table():
@@ -109,8 +91,7 @@ def render_overlay(result, frame, mask_alpha=0.5, no_mask=False, no_box=False, c
     out = torch.empty(H, W, 3, dtype=torch.uint8, device=dev)
     m = colors_dev = boxes_dev = None
     if n:
-        m = masks.contiguous()
-        m = m.view(torch.uint8) if m.dtype == torch.bool else m
+        m = _as_bytes(masks)
         colors_dev = _upload(color_table(n), torch.uint8, dev)
         boxes_dev = _upload(boxes, torch.int32, dev)
     alpha, one_minus = float(np.float32(mask_alpha)), float(np.float32(1 - mask_alpha))      # (the subtraction in double first, as the host code)

@@ -12,33 +12,15 @@ encode() reads the masks where the model left them and downloads the strings: tw
 totals, string lengths: 4 and 8 bytes per mask) and one of the packed strings, never a mask.  decode() parses on the host (vectorised
 numpy) and paints on the device.  The host helpers (counts_to_string, string_to_counts, area) need no GPU.
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from ._lib import check, lib
+from ._masks import _as_bytes, _describe, _p, _stream, _upload
 
 __all__ = ["encode", "decode", "counts_to_string", "string_to_counts", "area"]
 
 _MAX_GROUPS = 12                                             # 5-bit groups of one value the host parser takes (60 bits; 32-bit counts need 7)
-
-
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _upload(values, dtype, device):
-    """host values -> device tensor through page-locked memory (an asynchronous copy: no host synchronisation)"""
-    return torch.tensor(values, dtype=dtype).pin_memory().to(device, non_blocking=True)
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(device.index))
-
-
-def _describe(t):
-    return "%s %s %s" % (t.device, t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__
 
 
 # ---------------------------------------------------------------------------------------------------------------- host helpers
@@ -129,8 +111,7 @@ def _mask_list(masks):
         if not m.is_cuda or (ref is not None and m.device != ref.device):
             raise RuntimeError("masks[%d] must be a device tensor%s (the codec has no host path), got %s" %
                                (b, "" if ref is None else " on %s" % ref.device, _describe(m)))
-        m = m.contiguous()
-        m = m.view(torch.uint8) if m.dtype == torch.bool else m
+        m = _as_bytes(m)
         ref = m if ref is None else ref
         out.append(m)
     return out, ref
