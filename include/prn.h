@@ -759,6 +759,26 @@ int prn_planes_fit(const float* depth, const unsigned char* const* masks_dev, co
 int prn_planes_render(const float* depth, const unsigned char* const* masks_dev, const int* first_dev, const double* k_dev, const double* planes,
                       const unsigned char* valid, int B, int Ntot, int H, int W, int has_range, float lo, float hi, float* out, const void* ws, void* stream);
 
+/* ---- robust plane fit: RANSAC hypotheses scored per mask, least-squares refit on the inliers (csrc/prn_planes_ransac.hip) ----
+ * Inputs as prn_planes_fit.  For instance i (its index WITHIN ITS IMAGE) with `count` mask pixels and hypothesis h < hypotheses:
+ *   draws      Philox4x32-10, counter (h, 0, i, 0), key (seed lo, seed hi); words w0 w1 w2 -> ranks r_j = (w_j * count) >> 32; point j is the
+ *              r_j-th set pixel of the mask in row-major order, back-projected as in prn_planes_fit
+ *   hypothesis e1 = p1 - p0, e2 = p2 - p0, c = e1 x e2; degenerate unless c.c > 1e-12 (e1.e1)(e2.e2) (NaN fails); else n = c / |c|, d = n . p0
+ *   score      mask pixels with |n . X - d| <= t, t = threshold (metres) or threshold * Z of the pixel (relative != 0); a degenerate hypothesis
+ *              scores 0, a pixel with non-finite depth is never an inlier
+ *   choice     the largest score, the lowest h on ties; a best score below 3: the instance is invalid
+ *   refit      P0 = the prn_planes_fit plane of the chosen hypothesis's inliers; for r = 1 .. refine: S_r = mask pixels within t of P_{r-1},
+ *              P_r = the prn_planes_fit plane of S_r (an invalid P_{r-1} leaves the instance invalid)
+ * Outputs: planes / centroid / valid as prn_planes_fit, of the last inlier set; count [Ntot] int64 (pixels of the MASK), inliers [Ntot] int64
+ * (pixels of the last inlier set), hypothesis [Ntot] int32 (the chosen h), inlier_masks [Ntot][H][W] bytes (1 = inlier).  An invalid instance
+ * has a NaN plane and centroid, inliers 0, hypothesis -1 and an all-zero inlier mask.
+ * hypotheses 1 .. 4096, refine 0 .. 8, threshold finite and > 0.  ws: prn_planes_ransac_ws_bytes (-1: invalid sizes), 16-byte aligned.  Integer
+ * atomics only, no host synchronisation, nothing allocated: bit-identical run to run and between a batched call and per-image calls. */
+int64_t prn_planes_ransac_ws_bytes(int B, int Ntot, int H, int W, int hypotheses);
+int prn_planes_ransac_fit(const float* depth, const unsigned char* const* masks_dev, const int* first_dev, const double* k_dev, int B, int Ntot, int H, int W,
+                          double threshold, int relative, int hypotheses, int refine, unsigned long long seed, double* planes, double* centroid,
+                          unsigned char* valid, int64_t* count, int64_t* inliers, int* hypothesis, unsigned char* inlier_masks, void* ws, void* stream);
+
 /* ---- the inference overlay and the depth picture (csrc/prn_render.hip) ---------------------------------------------------------
  * What simple_inference.py drew on the host (display_on_frame, _viridis: N full-frame float passes per image), as device launches.
  * Overlay, ONE launch:

@@ -208,6 +208,8 @@ SIGNATURES = {
     "prn_planes_ws_bytes": (c_i64, [c_int] * 4),
     "prn_planes_fit": (c_int, [P] * 4 + [c_int] * 4 + [P] * 6),
     "prn_planes_render": (c_int, [P] * 6 + [c_int] * 5 + [c_float, c_float, P, P, P]),
+    "prn_planes_ransac_ws_bytes": (c_i64, [c_int] * 5),
+    "prn_planes_ransac_fit": (c_int, [P] * 4 + [c_int] * 4 + [ctypes.c_double, c_int, c_int, c_int, ctypes.c_uint64] + [P] * 9),
     "prn_render_overlay": (c_int, [P] * 4 + [c_int] * 3 + [c_float, c_float, c_int, P, P]),
     "prn_render_limits_ws_bytes": (c_i64, []),
     "prn_render_depth_limits": (c_int, [P, c_i64, ctypes.c_double, ctypes.c_double, P, P, P]),

@@ -59,10 +59,21 @@ def parse_args(argv=None):
     p.add_argument("--min_area", default=0, type=int, help="--clean_masks: components smaller than this are removed")
     p.add_argument("--fill_holes", action="store_true", help="--clean_masks: fill the holes of what was kept")
     p.add_argument("--connectivity", default=8, type=int, choices=[4, 8], help="--clean_masks: pixel connectivity of a component")
+    p.add_argument("--plane_fit", default="lsq", type=str, choices=["lsq", "ransac"],
+                   help="how --ibims1_pd fits each instance's plane: least squares over the whole mask, or RANSAC hypotheses scored on the device "
+                        "(planerecnet_amd.planes.fit_planes_ransac) with a least-squares refit on the inliers")
+    p.add_argument("--plane_threshold", default=0.05, type=float, help="--plane_fit ransac: inlier distance to the plane in metres")
+    p.add_argument("--plane_relative", action="store_true", help="--plane_fit ransac: the threshold is a fraction of each pixel's depth")
+    p.add_argument("--plane_hypotheses", default=256, type=int, help="--plane_fit ransac: three-point hypotheses per instance (1 .. 4096)")
+    p.add_argument("--plane_refine", default=1, type=int, help="--plane_fit ransac: rounds of re-selecting the inliers and fitting again (0 .. 8)")
+    p.add_argument("--plane_seed", default=0, type=int, help="--plane_fit ransac: seed of the draws")
     global args
     args = p.parse_args(argv)
     if args.contours and args.render != "device":
         p.error("--contours needs --render device")
+    if not (args.plane_threshold > 0 and args.plane_threshold < float("inf")) or not 1 <= args.plane_hypotheses <= 4096 or not 0 <= args.plane_refine <= 8 \
+            or args.plane_seed < 0:
+        p.error("--plane_threshold must be positive and finite, --plane_hypotheses 1 .. 4096, --plane_refine 0 .. 8, --plane_seed >= 0")
     if args.min_area < 0:
         p.error("--min_area must be >= 0")
     return args
@@ -73,6 +84,14 @@ def clean_options():
     if args.clean_masks == "off":
         return None
     return {"keep": args.clean_masks, "min_area": args.min_area, "fill_holes": args.fill_holes, "connectivity": args.connectivity}
+
+
+def robust_options():
+    """the planes.fit_planes_ransac keywords the flags ask for (None: --plane_fit lsq)"""
+    if args.plane_fit == "lsq":
+        return None
+    return {"threshold": args.plane_threshold, "relative": args.plane_relative, "hypotheses": args.plane_hypotheses, "refine": args.plane_refine,
+            "seed": args.plane_seed}
 
 
 def cleaned(results):
@@ -241,7 +260,7 @@ def _ibims1_export(net, in_folder, out_folder, planar):
         r = ibims1_results(net, rgb)
         if planar:
             from planerecnet_amd.planes import planar_depth
-            depth = planar_depth([r], k_matrix, depth_range=(0.0, 10.0), clean=clean_options())[0]["pred_plane_depth"]
+            depth = planar_depth([r], k_matrix, depth_range=(0.0, 10.0), clean=clean_options(), robust=robust_options())[0]["pred_plane_depth"]
         else:
             depth = r["pred_depth"]
         depth = depth.squeeze().float().cpu().numpy()
