@@ -392,9 +392,18 @@ __device__ __forceinline__ void focal_terms(float x, bool pos, float alpha, floa
   const float w = alpha >= 0.f ? (pos ? alpha : 1.f - alpha) : 1.f;
   const float qg = gamma == 2.f ? q * q : powf(q, gamma), qg1 = gamma == 2.f ? q : powf(q, gamma - 1.f);
   loss = w * ce * qg;
-  // d/dp_t [ -log(p_t) q^g ] = -q^g / p_t - g q^(g-1) (-log p_t) ... with -log p_t = ce ; d p_t / dx = +-p(1-p)
-  const float dpt = -qg / fmaxf(pt, 1e-38f) + gamma * qg1 * (-ce);
-  dldx = w * dpt * (pos ? 1.f : -1.f) * p * (1.f - p);
+  if (pt >= 1e-37f) {
+    // d/dp_t [ -log(p_t) q^g ] = -q^g / p_t - g q^(g-1) (-log p_t) ... with -log p_t = ce ; d p_t / dx = +-p(1-p)
+    const float dpt = -qg / fmaxf(pt, 1e-38f) + gamma * qg1 * (-ce);
+    dldx = w * dpt * (pos ? 1.f : -1.f) * p * (1.f - p);
+  } else {
+    // a confidently wrong cell (negative with x >= 16.7: fp32 p = 1; positive with x <= -85.2: p below 1e-37, denormal or 0): p_t and p(1-p) are both lost, and the form
+    // above gave 0 -- or, through its guard on the division, a fraction -- for the largest gradient there is, +-w.  Here without the division by p_t and
+    // without the common factor p(1-p):  d/dx [ ce q^g ] = (p - t) q^g + g q^(g-1) ce dq/dx  with d ce / dx = p - t and dq/dx = -+p(1-p).
+    // (Only here: elsewhere the form above is as accurate, and a training run's results stay what they were bit for bit.)
+    const float dq = (pos ? -1.f : 1.f) * p * (1.f - p);
+    dldx = w * ((p - (pos ? 1.f : 0.f)) * qg + gamma * qg1 * ce * dq);
+  }
 }
 
 __global__ __launch_bounds__(256) void focal_partial_kernel(const float* __restrict__ x, const int64_t* __restrict__ label, double* __restrict__ part,
@@ -497,7 +506,7 @@ __global__ __launch_bounds__(256) void rmse_log_bwd_kernel(const float* __restri
   const size_t k = (size_t)b * HW + i;
   const float gv = gt[k], pv = pred[k];
   float d = 0.f;
-  if (gv > min_depth && pv > clamp) d = g[0] * coef[b] * (logf(pv) - logf(fmaxf(gv, clamp))) / pv;     // (pred <= clamp: the clamp's gradient is 0)
+  if (gv > min_depth && pv >= clamp) d = g[0] * coef[b] * (logf(pv) - logf(fmaxf(gv, clamp))) / pv;    // (pred < clamp: the clamp's gradient is 0; torch.clamp passes it at equality)
   dpred[k] = d;
 }
 }  // namespace
