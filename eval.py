@@ -19,6 +19,11 @@ the flag and drops it): boxes to `--bbox_det_file`, masks to `--mask_det_file` a
 ground-truth mask iff min(mask IoU, boundary IoU) exceeds the threshold.  The bands (`--boundary_ratio` of the image diagonal wide) are eroded
 and compared on the device (planerecnet_amd/morphology.py, metrics.boundary_iou; include/prn.h: prn_boundary_iou).  Without the flag the
 output is what it was.
+
+`--plane_metrics` adds the plane-level figures of the PlaneNet / PlaneRCNN / PlaneRecNet tables: the segmentation scores RI, VOI and SC, and
+plane and pixel recall at depth-error thresholds 0.05 .. 1.0 m.  Per frame the masks are painted into two label maps and reduced to one small
+integer table on the device (planerecnet_amd/plane_eval.py; include/prn.h: prn_label_map, prn_label_overlap); the tables come down once, after
+the last frame.  Without the flag the output and the return value are what they were.
 """
 import argparse
 import json
@@ -59,6 +64,8 @@ def parse_args(argv=None):
                         help="(extension) Add a Boundary AP row to the table: a detection matches iff min(mask IoU, boundary IoU) exceeds the threshold.")
     parser.add_argument("--boundary_ratio", default=0.02, type=float,
                         help="With --boundary_ap: the band width as a share of the image diagonal (Boundary IoU's dilation ratio).")
+    parser.add_argument("--plane_metrics", dest="plane_metrics", action="store_true",
+                        help="(extension) Add the plane segmentation scores RI / VOI / SC and plane / pixel recall over depth-error thresholds.")
     parser.add_argument("--synthetic_size", default=16, type=int, help="(extension) frames in the synthetic dataset.")
     global args
     args = parser.parse_args(argv)
@@ -107,10 +114,12 @@ class Detections:
                 json.dump(data, f)
 
 
-def evaluate(net, dataset, during_training=False, eval_nums=-1, detections=None, boundary_ratio=None):
+def evaluate(net, dataset, during_training=False, eval_nums=-1, detections=None, boundary_ratio=None, plane_metrics=False):
     """Reference eval.py:63-130.  Returns (mAP table as calc_map returns it, {metric name: mean over the frames}).
     detections: a `Detections` collector every frame's detections are added to (eval.py --output_coco_json; train.py passes none).
-    boundary_ratio: add the Boundary AP row (eval.py --boundary_ap); the band width of a frame is this share of its ground-truth masks' diagonal."""
+    boundary_ratio: add the Boundary AP row (eval.py --boundary_ap); the band width of a frame is this share of its ground-truth masks' diagonal.
+    plane_metrics: add RI / VOI / SC and the plane / pixel recall curves (eval.py --plane_metrics) to the printout and, under the keys `RI`, `VOI`,
+    `SC`, `plane_recall`, `pixel_recall`, to the returned metrics."""
     from planerecnet_amd import metrics
     from planerecnet_amd.morphology import boundary_radius
     if args is None:
@@ -123,6 +132,10 @@ def evaluate(net, dataset, during_training=False, eval_nums=-1, detections=None,
     indices = indices[:eval_nums]
     dev = next(net.parameters()).device
     infos, ap_data, all_maps = [], metrics.new_ap_data(boundary=boundary_ratio is not None), None
+    planes = None
+    if plane_metrics:
+        from planerecnet_amd.plane_eval import PlaneEvalAccumulator
+        planes = PlaneEvalAccumulator()
     try:
         for it, image_idx in enumerate(indices):
             torch.cuda.synchronize(dev)
@@ -131,6 +144,8 @@ def evaluate(net, dataset, during_training=False, eval_nums=-1, detections=None,
             result = net(image.unsqueeze(0).to(dev))[0]
             gt_masks, gt_boxes, gt_classes = (gt_instances[k].to(dev) for k in ("masks", "boxes", "classes"))
             infos.append([float(v) for v in metrics.compute_depth_metrics(result["pred_depth"], gt_depth.to(dev), median_scaling=True)])
+            if planes is not None:                                  # (a frame without detections counts: nothing is recalled in it)
+                planes.add_frame(gt_masks, gt_depth.to(dev), result["pred_masks"], result["pred_depth"])
             if result["pred_masks"] is not None:
                 radius = None if boundary_ratio is None else boundary_radius(gt_masks.shape[-2], gt_masks.shape[-1], boundary_ratio)
                 metrics.compute_segmentation_metrics(ap_data, gt_masks, gt_boxes, gt_classes, result["pred_masks"], result["pred_boxes"],
@@ -151,7 +166,15 @@ def evaluate(net, dataset, during_training=False, eval_nums=-1, detections=None,
         print("Depth Metrics:")
         names = metrics.depth_metrics
         print(", ".join("{}: {:.5f}".format(n, v) for n, v in zip(names[:7], mean[:7])) + " \n{}: {:.5f}".format(names[7], mean[7]))
-        return all_maps, dict(zip(names, mean.tolist()))
+        depth_metrics = dict(zip(names, mean.tolist()))
+        if planes is not None:
+            res = planes.result()
+            print("Plane segmentation: RI: {:.5f}, VOI: {:.5f}, SC: {:.5f}".format(res["RI"], res["VOI"], res["SC"]))
+            print("depth m | " + " ".join("{:5.2f}".format(t) for t in res["thresholds"][1:]))
+            for row, key in (("plane", "plane_recall"), ("pixel", "pixel_recall")):
+                print("{:>7} | ".format(row) + " ".join("{:5.3f}".format(v) for v in res[key][1:]))
+            depth_metrics.update({k: res[k] for k in ("RI", "VOI", "SC", "plane_recall", "pixel_recall")})
+        return all_maps, depth_metrics
     except KeyboardInterrupt:
         print("Stopping...")
         return all_maps, {}
@@ -206,7 +229,7 @@ def main():
         net = net.to("cuda:0")
         detections = Detections() if args.output_coco_json else None
         evaluate(net, dataset, during_training=False, eval_nums=args.max_images, detections=detections,
-                 boundary_ratio=args.boundary_ratio if args.boundary_ap else None)
+                 boundary_ratio=args.boundary_ratio if args.boundary_ap else None, plane_metrics=args.plane_metrics)
         if detections is not None:
             detections.dump(args.bbox_det_file, args.mask_det_file)
             print("Wrote %d detections to %s and %s" % (len(detections.bbox_data), args.bbox_det_file, args.mask_det_file))

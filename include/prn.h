@@ -907,6 +907,33 @@ int64_t prn_boundary_iou_ws_bytes(int A, int B, int H, int W);
 int prn_boundary_iou(const unsigned char* masks_a, const unsigned char* masks_b, int A, int B, int H, int W, int radius, float* mask_iou, float* boundary_iou,
                      void* ws, void* stream);
 
+/* ---- plane-level evaluation: label maps of instance masks and the overlap tables of two label maps (csrc/prn_plane_eval.hip) --------
+ * prn_label_map paints a ragged batch of masks into int32 label maps, one launch: masks_dev a DEVICE array [B] of pointers to image b's
+ * [N_b][H][W] bytes (non-zero = set; never dereferenced for N_b = 0), first_dev a DEVICE array [B+1] of instance offsets (N_b = first[b+1] -
+ * first[b]); only read.  labels [B][H][W], every entry written: 0 = no mask, i + 1 = instance i of that image; where masks overlap,
+ * PRN_LABEL_FIRST_WINS gives the lowest index (the highest score: detections come sorted by score), PRN_LABEL_LAST_WINS the highest (the order
+ * prn_planes_render paints in).  N_b = 0 gives an all-zero map.  1 <= B <= 65535, H * W < 2^31.  prn_label_map_flat is the same launch for ONE
+ * image whose N >= 1 masks lie back to back at `masks`: no tables, so the caller uploads nothing.
+ * prn_label_overlap builds, for every image, the joint histogram of two label maps and the fixed-point depth-error sum of every cell:
+ *   count[img][a][b] += 1, wsum[img][a][b] += q   for every pixel with labels_a = a in [0, A] and labels_b = b in [0, B]; a pixel with either
+ *   label outside its range is dropped from both.  depth_a, depth_b [nimg][H][W] fp32 or BOTH NULL (then wsum stays as it was):
+ *   e = |depth_b - depth_a| in fp32, e = 0 where depth_a < 1e-4 (no ground truth), q = rint(fmin(e, 1024) * 2^20) as an unsigned integer
+ *   (NaN and anything above 1024 m count as 1024 m; the product is exact and the rounding ties-to-even, so q is reproducible bit for bit).
+ * count, wsum: [nimg][A+1][B+1] uint64, ZEROED BY THE CALLER (the call adds).  One launch: every thread adds runs of equal bins, into the
+ * workgroup's tables in LDS while (A + 1) * (B + 1) <= PRN_LABEL_OVERLAP_LDS_BINS (flushed with 64-bit atomics, non-zero bins only), straight
+ * into count / wsum above that.  Refused before any launch: A or B outside [0, 1023], H * W >= 2^24 (2^30 a pixel must fit 64 bits), a NULL
+ * label or output pointer, one depth pointer without the other, nimg outside [1, 65535].
+ * Both: no workgroup waits for another, the only atomics are integer adds: results are identical run to run and between a batched call and
+ * per-image calls.  No allocation and no synchronisation inside; everything runs on `stream`. */
+#define PRN_LABEL_FIRST_WINS 0
+#define PRN_LABEL_LAST_WINS 1
+#define PRN_LABEL_OVERLAP_LDS_BINS 4096
+int prn_label_overlap_lds_bins(void);
+int prn_label_map(const unsigned char* const* masks_dev, const int* first_dev, int B, int H, int W, int priority, int* labels, void* stream);
+int prn_label_map_flat(const unsigned char* masks, int N, int H, int W, int priority, int* labels, void* stream);
+int prn_label_overlap(const int* labels_a, const int* labels_b, const float* depth_a, const float* depth_b, int nimg, int H, int W, int A, int B,
+                      uint64_t* count, uint64_t* wsum, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -228,6 +228,10 @@ SIGNATURES = {
     "prn_morph": (c_int, [P, P] + [c_int] * 7 + [P] * 4),
     "prn_boundary_iou_ws_bytes": (c_i64, [c_int] * 4),
     "prn_boundary_iou": (c_int, [P, P] + [c_int] * 5 + [P] * 4),
+    "prn_label_overlap_lds_bins": (c_int, []),
+    "prn_label_map": (c_int, [P, P] + [c_int] * 4 + [P, P]),
+    "prn_label_map_flat": (c_int, [P] + [c_int] * 4 + [P, P]),
+    "prn_label_overlap": (c_int, [P, P, P, P] + [c_int] * 5 + [P, P, P]),
 }
 
 

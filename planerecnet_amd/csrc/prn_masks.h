@@ -35,6 +35,23 @@ __device__ __forceinline__ unsigned prn_mask_bits16(const unsigned char* __restr
   return bits;
 }
 
+// the 16-byte groups of N masks `stride` bytes apart (a thread that walks the masks of an image over its own pixels; stride < 0 walks down):
+// where every group takes its vector load -- p and the stride both multiples of 16 -- the N loads are issued before the first is tested: one
+// round trip for all of them, where a walk that tests a mask before it loads the next is a chain of N.  Anything else: group by group.
+template <int N>
+__device__ __forceinline__ void prn_mask_bits16_each(const unsigned char* p, int64_t stride, int64_t avail, unsigned (&bits)[N]) {
+  if (__builtin_expect(avail >= 16 && ((reinterpret_cast<uintptr_t>(p) | (uintptr_t)stride) & 15) == 0, 1)) {
+    uint4 v[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = *reinterpret_cast<const uint4*>(p + k * stride);
+#pragma unroll
+    for (int k = 0; k < N; ++k) bits[k] = prn_nz16(v[k]);
+  } else {
+#pragma unroll
+    for (int k = 0; k < N; ++k) bits[k] = prn_mask_bits16(p + k * stride, avail);
+  }
+}
+
 // two 16-byte groups, each under the rule on its own (p + 16 is aligned exactly when p is); where both take their vector load, the two loads
 // are issued together
 __device__ __forceinline__ unsigned prn_mask_bits32(const unsigned char* __restrict__ p, int64_t avail) {
