@@ -934,6 +934,35 @@ int prn_label_map_flat(const unsigned char* masks, int N, int H, int W, int prio
 int prn_label_overlap(const int* labels_a, const int* labels_b, const float* depth_a, const float* depth_b, int nimg, int H, int W, int A, int B,
                       uint64_t* count, uint64_t* wsum, void* stream);
 
+/* ---- triangle mesh and point cloud of a depth map (csrc/prn_mesh.hip) --------------------------------------------
+ * Per image: depth [H][W] fp32, labels [H][W] int32 or NULL (all 0), colors [H][W][3] bytes or NULL, k [9] fp64 (row-major K: fx = k[0],
+ * fy = k[4], cx = k[2], cy = k[5]; pixel indices are integers, as in prn_planes_*); B images back to back; only read.
+ *   valid pixel  z finite and lo < z < hi in fp32 (and label > 0 with PRN_MESH_PLANAR_ONLY)
+ *   vertex       one per valid pixel; id = the valid pixels before it in row-major order of its image.  X = ((double)u - cx) * z / fx,
+ *                Y = ((double)v - cy) * z / fy, Z = z: fp64 in this order, each rounded to fp32 once; it carries the pixel's label and colour
+ *   triangles    of the quad a = (v,u), b = (v+1,u), c = (v,u+1), d = (v+1,u+1) (v < H-1, u < W-1): t0 = (a,b,c), t1 = (c,b,d), both facing the
+ *                camera (y down, looking along +Z).  One is emitted iff its corners are valid, carry one label (PRN_MESH_SAME_LABEL) and
+ *                zmax - zmin <= max_gap (PRN_MESH_RELATIVE: <= max_gap * zmin), subtraction and product each rounded to fp32.  Face id = the
+ *                emitted triangles before it, row-major by quad, t0 before t1
+ * Outputs, sized by the caller at capacity and written up to the counts only: vertices [B][H W][3] fp32, vertex_labels [B][H W] int32,
+ * vertex_colors [B][H W][3] bytes (NULL iff colors is), faces [B][2 (H-1) (W-1)][3] int32 vertex ids; every entry of vertex_id [B][H][W]
+ * (the vertex id, -1 for an invalid pixel) and of counts [B][2] = (vertices, triangles) is written.  Without PRN_MESH_FACES (the point
+ * cloud) no triangle is counted or written and `faces` is not read.  ws: prn_mesh_ws_bytes(B, H, W) bytes, 8-byte aligned.
+ * Four launches (three without faces) whatever B: per-workgroup counts of prn_mesh_block_pixels() consecutive pixels (64-bit ballots), one
+ * exclusive scan per image in chunks of prn_mesh_scan_chunk() workgroups, the vertex pass, the face pass.  No atomics, no workgroup waits
+ * for another: identical run to run and between a batched call and per-image calls.  No allocation and no synchronisation inside.
+ * Refused before any launch: H * W >= 2^24, B outside [1, 65535], a size <= 0, max_gap negative or not finite, unknown flags, a NULL among
+ * the required pointers, colors without vertex_colors or the reverse (prn_mesh_ws_bytes: -1 for refused sizes). */
+#define PRN_MESH_RELATIVE 1
+#define PRN_MESH_SAME_LABEL 2
+#define PRN_MESH_PLANAR_ONLY 4
+#define PRN_MESH_FACES 8
+int prn_mesh_block_pixels(void);
+int prn_mesh_scan_chunk(void);
+int64_t prn_mesh_ws_bytes(int B, int H, int W);
+int prn_mesh(const float* depth, const int* labels, const unsigned char* colors, const double* k, int B, int H, int W, float lo, float hi, float max_gap,
+             int flags, void* ws, float* vertices, int* vertex_labels, unsigned char* vertex_colors, int* vertex_id, int* faces, int* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

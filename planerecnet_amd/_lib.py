@@ -232,6 +232,10 @@ SIGNATURES = {
     "prn_label_map": (c_int, [P, P] + [c_int] * 4 + [P, P]),
     "prn_label_map_flat": (c_int, [P] + [c_int] * 4 + [P, P]),
     "prn_label_overlap": (c_int, [P, P, P, P] + [c_int] * 5 + [P, P, P]),
+    "prn_mesh_block_pixels": (c_int, []),
+    "prn_mesh_scan_chunk": (c_int, []),
+    "prn_mesh_ws_bytes": (c_i64, [c_int] * 3),
+    "prn_mesh": (c_int, [P] * 4 + [c_int] * 3 + [c_float] * 3 + [c_int] + [P] * 8),
 }
 
 

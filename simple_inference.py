@@ -18,6 +18,11 @@ every detected plane's depth replaces the prediction under its mask), values <= 
 rgb array enters FastBaseTransform as if it were BGR, as in the reference.  Deviation: the preview's 1 / 99 % limits come from
 np.nanpercentile (the reference's np.percentile turns a NaN-holding map into a meaningless image).  scipy is needed for these
 two flags only.
+
+`--ply` (not in the reference; default off) also writes the reconstruction as a PLY triangle mesh (planerecnet_amd.reconstruct: one vertex
+per pixel with a usable depth, the triangles of neighbouring pixels of one plane within --ply_gap of each other in depth): with the iBims-1
+exporters `out/<name>_mesh.ply` from the depth that exporter writes, the file's RGB and the owner map of the masks; with --image
+`<output>_mesh.ply`, which needs the camera as --intrinsics fx,fy,cx,cy.
 """
 import argparse
 import os
@@ -67,6 +72,13 @@ def parse_args(argv=None):
     p.add_argument("--plane_hypotheses", default=256, type=int, help="--plane_fit ransac: three-point hypotheses per instance (1 .. 4096)")
     p.add_argument("--plane_refine", default=1, type=int, help="--plane_fit ransac: rounds of re-selecting the inliers and fitting again (0 .. 8)")
     p.add_argument("--plane_seed", default=0, type=int, help="--plane_fit ransac: seed of the draws")
+    p.add_argument("--ply", action="store_true",
+                   help="also write the reconstruction as a PLY triangle mesh (planerecnet_amd.reconstruct): out/<name>_mesh.ply with --ibims1 / --ibims1_pd, "
+                        "<output>_mesh.ply with --image (which then needs --intrinsics)")
+    p.add_argument("--ply_gap", default=0.05, type=float, help="--ply: the largest depth spread of a triangle's corners, as a fraction of their smallest depth")
+    p.add_argument("--ply_absolute", action="store_true", help="--ply: --ply_gap is in metres")
+    p.add_argument("--ply_planar_only", action="store_true", help="--ply: only pixels a detected plane owns become vertices")
+    p.add_argument("--intrinsics", default=None, type=str, help="fx,fy,cx,cy of the --image file in pixels of that file (--ply)")
     global args
     args = p.parse_args(argv)
     if args.contours and args.render != "device":
@@ -76,7 +88,39 @@ def parse_args(argv=None):
         p.error("--plane_threshold must be positive and finite, --plane_hypotheses 1 .. 4096, --plane_refine 0 .. 8, --plane_seed >= 0")
     if args.min_area < 0:
         p.error("--min_area must be >= 0")
+    if args.intrinsics is not None:
+        try:
+            args.intrinsics = tuple(float(v) for v in args.intrinsics.split(","))
+        except ValueError:
+            args.intrinsics = ()
+        if len(args.intrinsics) != 4 or not all(v == v and abs(v) < float("inf") for v in args.intrinsics):
+            p.error("--intrinsics must be four finite numbers fx,fy,cx,cy")
+    if args.ply:
+        if args.ibims1 is None and args.ibims1_pd is None and args.image is None:
+            p.error("--ply goes with --ibims1, --ibims1_pd or --image")
+        if args.image is not None and args.intrinsics is None:
+            p.error("--ply with --image needs --intrinsics fx,fy,cx,cy: a single image carries no camera")
+        if not (args.ply_gap >= 0 and args.ply_gap < float("inf")):
+            p.error("--ply_gap must be finite and >= 0")
     return args
+
+
+def mesh_options():
+    """the reconstruct.mesh keywords the --ply flags ask for"""
+    return {"max_gap": args.ply_gap, "relative": not args.ply_absolute, "planar_only": args.ply_planar_only}
+
+
+def ibims1_mesh_path(out_folder, name):
+    """<name>_mesh.ply in out_folder"""
+    return os.path.join(out_folder, name + "_mesh.ply")
+
+
+def write_mesh(path, result, k_matrix, rgb, comment=None):
+    """--ply: one result dict (its "pred_plane_depth" if present, else "pred_depth"; labels = the owner map of its masks) -> a PLY file;
+    rgb: uint8 [H,W,3] array or tensor in the order the file shall hold"""
+    from planerecnet_amd.reconstruct import reconstruct_results, write_ply
+    m = reconstruct_results([result], k_matrix, frames=[torch.as_tensor(rgb)], **mesh_options())
+    write_ply(path, m.cpu()[0], binary=True, comment=comment)
 
 
 def clean_options():
@@ -185,6 +229,19 @@ def inference_image(net, path, save_path=None, depth_mode="colored"):
     name, ext = os.path.splitext(path if save_path is None else save_path)
     save_path = name + "_seg" + ext if save_path is None else save_path
     depth_path = name + "_dep.png"
+    if args.ply:
+        # the depth lives on the resized (and zero-padded) frame: the mesh is cut to the resized picture, the intrinsics follow the resize
+        # (pixel centres: x' = (x + 0.5) s - 0.5), the colours are that picture's
+        Wr, Hr = calc_size_preserve_ar(W, H, cfg.max_size)
+        fx, fy, cx, cy = args.intrinsics
+        sx, sy = Wr / W, Hr / H
+        k_matrix = np.array([[fx * sx, 0.0, (cx + 0.5) * sx - 0.5], [0.0, fy * sy, (cy + 0.5) * sy - 0.5], [0.0, 0.0, 1.0]])
+        r = dict(results[0])
+        r["pred_depth"] = r["pred_depth"][..., :Hr, :Wr]
+        if r.get("pred_masks") is not None:
+            r["pred_masks"] = r["pred_masks"][:, :Hr, :Wr]
+        rgb = frame[:Hr, :Wr].flip(-1).round().clamp(0, 255).to(torch.uint8)
+        write_mesh(os.path.splitext(save_path)[0] + "_mesh.ply", r, k_matrix, rgb, comment="PlaneRecNet " + os.path.basename(path))
     if args.render == "device":
         blended, depth_image = display_on_device(results[0], frame, depth_mode=depth_mode, depth_shift=args.depth_shift, no_mask=args.no_mask,
                                                  no_box=args.no_box, no_text=args.no_text, contours=args.contours)
@@ -260,9 +317,15 @@ def _ibims1_export(net, in_folder, out_folder, planar):
         r = ibims1_results(net, rgb)
         if planar:
             from planerecnet_amd.planes import planar_depth
-            depth = planar_depth([r], k_matrix, depth_range=(0.0, 10.0), clean=clean_options(), robust=robust_options())[0]["pred_plane_depth"]
+            planar_out = planar_depth([r], k_matrix, depth_range=(0.0, 10.0), clean=clean_options(), robust=robust_options())[0]
+            depth = planar_out["pred_plane_depth"]
         else:
             depth = r["pred_depth"]
+        if args.ply:
+            shown = dict(r)
+            if planar:
+                shown.update({k: v for k, v in planar_out.items() if k in ("pred_plane_depth", "pred_plane_masks")})
+            write_mesh(ibims1_mesh_path(out_folder, name), shown, k_matrix, rgb, comment="PlaneRecNet " + os.path.basename(path))
         depth = depth.squeeze().float().cpu().numpy()
         out, preview = ibims1_outputs(out_folder, name)
         sio.savemat(out, {"pred_depths": depth})
