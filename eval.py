@@ -24,6 +24,13 @@ output is what it was.
 plane and pixel recall at depth-error thresholds 0.05 .. 1.0 m.  Per frame the masks are painted into two label maps and reduced to one small
 integer table on the device (planerecnet_amd/plane_eval.py; include/prn.h: prn_label_map, prn_label_overlap); the tables come down once, after
 the last frame.  Without the flag the output and the return value are what they were.
+
+`--normal_metrics` adds the surface-normal figures such work is judged by: the mean, median and RMS angle between the normals of the predicted
+depth and of the ground-truth depth -- the pair the depth errors compare, under the dataset's intrinsics, no labels -- and the shares of pixels
+within 11.25 / 22.5 / 30 degrees, pooled over all frames' pixels.  Both normal maps and the error histogram are computed on the device
+(planerecnet_amd/normals.py; include/prn.h: prn_normals, prn_normal_error); the tables come down once, after the last frame.  No median scaling:
+under the relative gap (`--normal_gap`, a fraction of the smaller depth) the normals do not depend on a global depth scale.  Without the flag the
+output and the return value are what they were.
 """
 import argparse
 import json
@@ -66,6 +73,11 @@ def parse_args(argv=None):
                         help="With --boundary_ap: the band width as a share of the image diagonal (Boundary IoU's dilation ratio).")
     parser.add_argument("--plane_metrics", dest="plane_metrics", action="store_true",
                         help="(extension) Add the plane segmentation scores RI / VOI / SC and plane / pixel recall over depth-error thresholds.")
+    parser.add_argument("--normal_metrics", dest="normal_metrics", action="store_true",
+                        help="(extension) Add the angular error of the predicted depth's surface normals against the ground-truth depth's.")
+    parser.add_argument("--normal_step", default=1, type=int, help="With --normal_metrics: the neighbours' distance in pixels.")
+    parser.add_argument("--normal_gap", default=0.05, type=float,
+                        help="With --normal_metrics: the largest depth spread of a pixel and a neighbour it uses, as a fraction of the smaller depth.")
     parser.add_argument("--synthetic_size", default=16, type=int, help="(extension) frames in the synthetic dataset.")
     global args
     args = parser.parse_args(argv)
@@ -114,12 +126,15 @@ class Detections:
                 json.dump(data, f)
 
 
-def evaluate(net, dataset, during_training=False, eval_nums=-1, detections=None, boundary_ratio=None, plane_metrics=False):
+def evaluate(net, dataset, during_training=False, eval_nums=-1, detections=None, boundary_ratio=None, plane_metrics=False, normal_metrics=False):
     """Reference eval.py:63-130.  Returns (mAP table as calc_map returns it, {metric name: mean over the frames}).
     detections: a `Detections` collector every frame's detections are added to (eval.py --output_coco_json; train.py passes none).
     boundary_ratio: add the Boundary AP row (eval.py --boundary_ap); the band width of a frame is this share of its ground-truth masks' diagonal.
     plane_metrics: add RI / VOI / SC and the plane / pixel recall curves (eval.py --plane_metrics) to the printout and, under the keys `RI`, `VOI`,
-    `SC`, `plane_recall`, `pixel_recall`, to the returned metrics."""
+    `SC`, `plane_recall`, `pixel_recall`, to the returned metrics.
+    normal_metrics: add the angular error of the predicted depth's normals against the ground-truth depth's (eval.py --normal_metrics; step and gap
+    from --normal_step / --normal_gap) to the printout and, under the keys `normal_mean`, `normal_median`, `normal_rmse`, `normal_11.25`, `normal_22.5`,
+    `normal_30`, `normal_pixels`, to the returned metrics."""
     from planerecnet_amd import metrics
     from planerecnet_amd.morphology import boundary_radius
     if args is None:
@@ -136,6 +151,11 @@ def evaluate(net, dataset, during_training=False, eval_nums=-1, detections=None,
     if plane_metrics:
         from planerecnet_amd.plane_eval import PlaneEvalAccumulator
         planes = PlaneEvalAccumulator()
+    normal_acc = None
+    if normal_metrics:
+        from planerecnet_amd import normals
+        normal_acc = normals.NormalErrorAccumulator((11.25, 22.5, 30), device=dev)
+        normal_kw = {"step": getattr(args, "normal_step", 1), "max_gap": getattr(args, "normal_gap", 0.05)}
     try:
         for it, image_idx in enumerate(indices):
             torch.cuda.synchronize(dev)
@@ -146,6 +166,9 @@ def evaluate(net, dataset, during_training=False, eval_nums=-1, detections=None,
             infos.append([float(v) for v in metrics.compute_depth_metrics(result["pred_depth"], gt_depth.to(dev), median_scaling=True)])
             if planes is not None:                                  # (a frame without detections counts: nothing is recalled in it)
                 planes.add_frame(gt_masks, gt_depth.to(dev), result["pred_masks"], result["pred_depth"])
+            if normal_acc is not None:
+                maps = [normals.from_depth(d.float().reshape(d.shape[-2:]), gt_instances["k_matrix"], **normal_kw) for d in (result["pred_depth"], gt_depth.to(dev))]
+                normal_acc.add(maps[0][0], maps[0][1], maps[1][0], maps[1][1])
             if result["pred_masks"] is not None:
                 radius = None if boundary_ratio is None else boundary_radius(gt_masks.shape[-2], gt_masks.shape[-1], boundary_ratio)
                 metrics.compute_segmentation_metrics(ap_data, gt_masks, gt_boxes, gt_classes, result["pred_masks"], result["pred_boxes"],
@@ -174,6 +197,12 @@ def evaluate(net, dataset, during_training=False, eval_nums=-1, detections=None,
             for row, key in (("plane", "plane_recall"), ("pixel", "pixel_recall")):
                 print("{:>7} | ".format(row) + " ".join("{:5.3f}".format(v) for v in res[key][1:]))
             depth_metrics.update({k: res[k] for k in ("RI", "VOI", "SC", "plane_recall", "pixel_recall")})
+        if normal_acc is not None:
+            res = normal_acc.result()
+            print("Normal Metrics:")
+            print("mean: {:.5f}, median: {:.5f}, rmse: {:.5f}, 11.25: {:.5f}, 22.5: {:.5f}, 30: {:.5f}".format(res["mean"], res["median"], res["rmse"], *res["within"]))
+            depth_metrics.update({"normal_mean": res["mean"], "normal_median": res["median"], "normal_rmse": res["rmse"], "normal_11.25": float(res["within"][0]),
+                                  "normal_22.5": float(res["within"][1]), "normal_30": float(res["within"][2]), "normal_pixels": res["count"]})
         return all_maps, depth_metrics
     except KeyboardInterrupt:
         print("Stopping...")
@@ -229,7 +258,7 @@ def main():
         net = net.to("cuda:0")
         detections = Detections() if args.output_coco_json else None
         evaluate(net, dataset, during_training=False, eval_nums=args.max_images, detections=detections,
-                 boundary_ratio=args.boundary_ratio if args.boundary_ap else None, plane_metrics=args.plane_metrics)
+                 boundary_ratio=args.boundary_ratio if args.boundary_ap else None, plane_metrics=args.plane_metrics, normal_metrics=args.normal_metrics)
         if detections is not None:
             detections.dump(args.bbox_det_file, args.mask_det_file)
             print("Wrote %d detections to %s and %s" % (len(detections.bbox_data), args.bbox_det_file, args.mask_det_file))

@@ -963,6 +963,46 @@ int64_t prn_mesh_ws_bytes(int B, int H, int W);
 int prn_mesh(const float* depth, const int* labels, const unsigned char* colors, const double* k, int B, int H, int W, float lo, float hi, float max_gap,
              int flags, void* ws, float* vertices, int* vertex_labels, unsigned char* vertex_colors, int* vertex_id, int* faces, int* counts, void* stream);
 
+/* ---- surface normals of a depth map and their angular error (csrc/prn_normals.hip) -----------------------------
+ * Per image: depth [H][W] fp32, labels [H][W] int32 or NULL, k [9] fp64 as in prn_mesh; B images back to back; only read.
+ *   valid pixel  z finite and lo < z < hi in fp32
+ *   point        P = (((double)u - cx) * z / fx, ((double)v - cy) * z / fy, z), fp64 in this order, NOT rounded to fp32
+ *   usable q     a neighbour q of the centre c is usable iff it is inside the image and valid, label[q] == label[c] (labels given and
+ *                PRN_NORMALS_SAME_LABEL) and zmax - zmin <= max_gap (PRN_NORMALS_RELATIVE: <= max_gap * zmin) over the two depths,
+ *                subtraction and product each rounded to fp32
+ *   tangents     tu from E = (v, u+step), W = (v, u-step): P(E) - P(W) if both are usable, P(E) - P(c) / P(c) - P(W) if one is, else the pixel
+ *                has no normal; tv the same from S = (v+step, u), N = (v-step, u)
+ *   normal       n = tv x tu, every product and difference rounded to fp64 on its own (nothing fused); L2 = (nx nx + ny ny) + nz nz; no
+ *                normal unless the centre is valid and L2 is finite and > 0; output n / sqrt(L2) per component (negated with
+ *                PRN_NORMALS_PLANE_SIGN: prn_planes_*'s n . X = d >= 0; otherwise n . P < 0, the side of prn_mesh's triangles), each
+ *                rounded to fp32 once.  Pixels without a normal hold (0,0,0) and valid = 0
+ * Outputs, every entry written: normals [B][H][W][3] fp32, valid [B][H][W] bytes (0 / 1), image [B][H][W][3] bytes or NULL: BGR with
+ * channel 0 = z, 1 = y, 2 = x, each rint(((double)n_c * 0.5 + 0.5) * 255.0) of the fp32 component (ties to even), (0,0,0) without a normal.
+ * One launch whatever B: the image is the grid's y, a workgroup takes prn_normals_block_pixels() consecutive row-major pixels, one a thread;
+ * records and colours are staged in LDS and leave as whole dwords.  No atomics; identical run to run.
+ * Refused before any launch: H * W >= 2^24, a size <= 0, B outside [1, 65535], step < 1, max_gap negative or not finite, unknown flags, a
+ * NULL among depth, k, normals, valid.
+ *
+ * prn_normal_error: over the n pixels of each of B image pairs that are valid in both maps (a, b: [B][n][3] fp32, valid_a, valid_b: [B][n]
+ * bytes): d = (double)a - (double)b per component, d2 = (dx dx + dy dy) + dz dz (nothing fused), chord = sqrt(d2),
+ * bin = min(BINS - 1, (int)floor(chord * (BINS / 2))) (a NaN chord: the last bin), BINS = prn_normal_error_bins().  ADDS into
+ * hist [B][BINS], within [B][T] (pixels with d2 <= thr2[t]; thr2: T <= PRN_NORMAL_ERROR_MAX_T doubles on the HOST, passed on by value) and
+ * count [B], all int64, which the caller zeroes: an accumulator keeps a run's totals on the device.  A workgroup gathers a uint32
+ * histogram of its pixels in LDS and flushes the non-zero bins with 64-bit integer atomics; within / count come from wave ballots.  Integer
+ * atomics only, no workgroup waits for another: identical run to run.  Refused: B outside [1, 65535], n outside [1, 2^31), T outside
+ * [0, PRN_NORMAL_ERROR_MAX_T], thr2 NULL with T > 0, a NULL among the other pointers.
+ * Neither allocates or synchronises. */
+#define PRN_NORMALS_RELATIVE 1
+#define PRN_NORMALS_SAME_LABEL 2
+#define PRN_NORMALS_PLANE_SIGN 4
+#define PRN_NORMAL_ERROR_MAX_T 8
+int prn_normals_block_pixels(void);
+int prn_normal_error_bins(void);
+int prn_normals(const float* depth, const int* labels, const double* k, int B, int H, int W, int step, float lo, float hi, float max_gap, int flags,
+                float* normals, unsigned char* valid, unsigned char* image, void* stream);
+int prn_normal_error(const float* a, const unsigned char* valid_a, const float* b, const unsigned char* valid_b, int B, int64_t n, const double* thr2, int T,
+                     int64_t* hist, int64_t* within, int64_t* count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -236,6 +236,10 @@ SIGNATURES = {
     "prn_mesh_scan_chunk": (c_int, []),
     "prn_mesh_ws_bytes": (c_i64, [c_int] * 3),
     "prn_mesh": (c_int, [P] * 4 + [c_int] * 3 + [c_float] * 3 + [c_int] + [P] * 8),
+    "prn_normals_block_pixels": (c_int, []),
+    "prn_normal_error_bins": (c_int, []),
+    "prn_normals": (c_int, [P] * 3 + [c_int] * 4 + [c_float] * 3 + [c_int] + [P] * 4),
+    "prn_normal_error": (c_int, [P] * 4 + [c_int, c_i64, P, c_int] + [P] * 4),
 }
 
 

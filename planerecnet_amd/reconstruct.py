@@ -25,7 +25,7 @@ import torch
 
 from ._masks import _bytes_buffer, _describe, _p, _stream
 
-__all__ = ["mesh", "point_cloud", "Mesh", "write_ply", "read_ply", "reconstruct_results", "block_pixels", "scan_chunk", "MAX_PIXELS"]
+__all__ = ["mesh", "point_cloud", "Mesh", "write_ply", "read_ply", "reconstruct_results", "results_depth_labels", "block_pixels", "scan_chunk", "MAX_PIXELS"]
 
 MAX_PIXELS = 1 << 24               # H * W stays below this
 RELATIVE, SAME_LABEL, PLANAR_ONLY, FACES = 1, 2, 4, 8      # include/prn.h: PRN_MESH_*
@@ -47,17 +47,22 @@ def scan_chunk():
 class Mesh:
     """What `mesh` returns, at capacity (cap = H W vertices, capf = 2 (H-1) (W-1) faces an image); rows past the counts are unspecified.
       vertices [B,cap,3] fp32   labels [B,cap] int32   colors [B,cap,3] uint8 or None   faces [B,capf,3] int32 or None (point cloud)
-      counts [B,2] int32 = (vertices, faces) of each image   vertex_id [B,H,W] int32: a pixel's vertex id, -1 where it is invalid"""
-    __slots__ = ("vertices", "labels", "colors", "faces", "counts", "vertex_id")
+      counts [B,2] int32 = (vertices, faces) of each image   vertex_id [B,H,W] int32: a pixel's vertex id, -1 where it is invalid
+      normals [B,cap,3] fp32 or None: each vertex's pixel's normal, where `mesh` was given a normal map"""
+    __slots__ = ("vertices", "labels", "colors", "faces", "counts", "vertex_id", "normals")
 
-    def __init__(self, vertices, labels, colors, faces, counts, vertex_id):
+    def __init__(self, vertices, labels, colors, faces, counts, vertex_id, normals=None):
         self.vertices, self.labels, self.colors, self.faces, self.counts, self.vertex_id = vertices, labels, colors, faces, counts, vertex_id
+        self.normals = normals
 
     def cpu(self):
         """-> one dict per image: "vertices" [Nv,3] float32, "faces" [Nf,3] int32 or None, "labels" [Nv] int32, "colors" [Nv,3] uint8 or None, as
-        numpy arrays trimmed to the counts.  Two downloads at most: the counts, then the trimmed ranges of every array in one buffer."""
+        numpy arrays trimmed to the counts, and "normals" [Nv,3] float32 only where the mesh has them.  Two downloads at most: the counts, then
+        the trimmed ranges of every array in one buffer."""
         counts = self.counts.cpu().numpy()
         fields = [("vertices", self.vertices, 0), ("faces", self.faces, 1), ("labels", self.labels, 0), ("colors", self.colors, 0)]
+        if self.normals is not None:
+            fields.append(("normals", self.normals, 0))
         parts, plan = [], []
         for b in range(counts.shape[0]):
             for name, t, which in fields:
@@ -146,7 +151,7 @@ def _intrinsics_np(k_matrix, B):
 
 @torch.no_grad()
 def mesh(depth, k_matrix, labels=None, colors=None, depth_range=(0.0, math.inf), max_gap=0.05, relative=True, same_label=True, planar_only=False,
-         faces=True):
+         faces=True, normals=None):
     """The triangle mesh of a depth map (module docstring for the rules).
 
     depth        [H,W], [1,H,W] or [B,1,H,W] fp32; H * W < 2^24
@@ -157,10 +162,14 @@ def mesh(depth, k_matrix, labels=None, colors=None, depth_range=(0.0, math.inf),
     max_gap      the largest depth spread of a triangle's corners: a fraction of their smallest depth (relative) or metres; finite, >= 0
     same_label   a triangle's corners carry one label        planar_only   only pixels with label > 0 are valid
     faces        False: the point cloud alone -- no face pass, Mesh.faces is None and counts[:, 1] is 0
+    normals      fp32 [H,W,3] or [B,H,W,3] on depth's device (normals.from_depth's map): Mesh.normals holds each vertex's pixel's row
     -> Mesh, on depth's device.  Nothing is read back: the arrays have capacity size and the counts say how much of them is written."""
     what = "mesh"
     B, H, W, lo, hi, gap = _check_inputs(depth, labels, colors, depth_range, max_gap, what)
     dev = depth.device
+    if normals is not None and not (torch.is_tensor(normals) and normals.dtype == torch.float32 and normals.device == dev and
+                                    tuple(normals.shape) in ((B, H, W, 3),) + (((H, W, 3),) if B == 1 else ())):
+        raise RuntimeError("%s: normals must be an fp32 [H,W,3] or [B,H,W,3] tensor (B=%d H=%d W=%d) on %s, got %s" % (what, B, H, W, dev, _describe(normals)))
     cap, capf = H * W, 2 * (H - 1) * (W - 1)
     z = depth.detach().reshape(B, H, W).contiguous()
     lab = None if labels is None else labels.reshape(B, H, W).contiguous()
@@ -185,6 +194,7 @@ def mesh(depth, k_matrix, labels=None, colors=None, depth_range=(0.0, math.inf),
                 out.counts[b, 1] = tri.shape[0]
             out.counts[b, 0] = nv
             out.vertex_id[b] = torch.from_numpy(vid)
+        out.normals = _vertex_rows(normals, out.vertex_id)
         return out
     from ._lib import check, lib
     from .planes import _intrinsics
@@ -202,29 +212,38 @@ def mesh(depth, k_matrix, labels=None, colors=None, depth_range=(0.0, math.inf),
                            float(gap), flags, _p(ws), _p(out.vertices[b0:]), _p(out.labels[b0:]), None if col is None else _p(out.colors[b0:]),
                            _p(out.vertex_id[b0:]), _p(out.faces[b0:]) if faces and capf else None, _p(out.counts[b0:]), stream), "prn_mesh")
         del ws                                                       # (stream-ordered allocator: reuse after this point is ordered behind the launches)
+    out.normals = _vertex_rows(normals, out.vertex_id)
     return out
 
 
-def point_cloud(depth, k_matrix, labels=None, colors=None, depth_range=(0.0, math.inf), planar_only=False):
+def _vertex_rows(pixel_map, vertex_id):
+    """a per-pixel map [B,H,W,3] (or [H,W,3], B = 1) -> its rows in vertex order [B,cap,3]: a scatter through the id map in tensor ops on the
+    map's device (no synchronisation; invalid pixels go to a row past the capacity that is cut off); rows past the counts are zero"""
+    if pixel_map is None:
+        return None
+    B, H, W = vertex_id.shape
+    cap = H * W
+    idx = vertex_id.reshape(B, cap).long()
+    idx = torch.where(idx < 0, torch.full_like(idx, cap), idx)
+    rows = torch.zeros(B, cap + 1, 3, dtype=pixel_map.dtype, device=pixel_map.device)
+    rows.scatter_(1, idx[..., None].expand(B, cap, 3), pixel_map.detach().reshape(B, cap, 3))
+    return rows[:, :cap].contiguous()
+
+
+def point_cloud(depth, k_matrix, labels=None, colors=None, depth_range=(0.0, math.inf), planar_only=False, normals=None):
     """The point cloud alone: `mesh` with faces=False (one vertex per valid pixel, no face pass)."""
-    return mesh(depth, k_matrix, labels=labels, colors=colors, depth_range=depth_range, planar_only=planar_only, faces=False)
+    return mesh(depth, k_matrix, labels=labels, colors=colors, depth_range=depth_range, planar_only=planar_only, faces=False, normals=normals)
 
 
 # ---- from the network's results --------------------------------------------------------------------------------------------------------
 
 @torch.no_grad()
-def reconstruct_results(results, k_matrix, frames=None, **mesh_kwargs):
-    """The mesh of planes.planar_depth's (or the network's) per-image result dicts, as one batch.
-      depth    "pred_plane_depth" where a dict has it, else "pred_depth"
-      labels   plane_eval.label_map(masks, "last") of "pred_plane_masks" where present, else "pred_masks" -- the owner of every pixel in
-               the order planar_depth paints; an image without detections has label 0 everywhere
-      colours  frames: None, a uint8 [B,H,W,3] tensor / array, or a list of B [H,W,3] ones (moved to the depth's device)
-    mesh_kwargs go to `mesh`.  -> Mesh"""
+def results_depth_labels(results):
+    """per-image result dicts -> (depth [B,1,H,W] fp32, labels [B,H,W] int32): what reconstruct_results meshes (its docstring)"""
     from . import plane_eval
     depth = torch.cat([(r["pred_plane_depth"] if r.get("pred_plane_depth") is not None else r["pred_depth"]).reshape(1, 1, *r["pred_depth"].shape[-2:])
                        for r in results]).float()
     B, _, H, W = depth.shape
-    dev = depth.device
     masks = []
     for r in results:
         m = r.get("pred_plane_masks") if r.get("pred_plane_masks") is not None else r.get("pred_masks")
@@ -232,15 +251,31 @@ def reconstruct_results(results, k_matrix, frames=None, **mesh_kwargs):
             m = m != 0
         masks.append(None if m is None or m.shape[0] == 0 else m)
     if any(m is not None for m in masks):
-        labels = plane_eval.label_map(masks, "last")
-    else:
-        labels = torch.zeros(B, H, W, dtype=torch.int32, device=dev)
+        return depth, plane_eval.label_map(masks, "last")
+    return depth, torch.zeros(B, H, W, dtype=torch.int32, device=depth.device)
+
+
+@torch.no_grad()
+def reconstruct_results(results, k_matrix, frames=None, normals=None, **mesh_kwargs):
+    """The mesh of planes.planar_depth's (or the network's) per-image result dicts, as one batch.
+      depth    "pred_plane_depth" where a dict has it, else "pred_depth"
+      labels   plane_eval.label_map(masks, "last") of "pred_plane_masks" where present, else "pred_masks" -- the owner of every pixel in
+               the order planar_depth paints; an image without detections has label 0 everywhere
+      colours  frames: None, a uint8 [B,H,W,3] tensor / array, or a list of B [H,W,3] ones (moved to the depth's device)
+      normals  None, or a dict of normals.from_depth keywords ({} = its defaults): the normals of the depth and labels that are meshed
+               go to the vertices (Mesh.normals)
+    mesh_kwargs go to `mesh`.  -> Mesh"""
+    depth, labels = results_depth_labels(results)
+    dev = depth.device
     colors = None
     if frames is not None:
         if isinstance(frames, (list, tuple)):
             frames = torch.stack([torch.as_tensor(f) for f in frames])
         colors = torch.as_tensor(frames).to(dev)
-    return mesh(depth, k_matrix, labels=labels, colors=colors, **mesh_kwargs)
+    if normals is not None:
+        from . import normals as _normals
+        normals = _normals.from_depth(depth, k_matrix, labels=labels, **dict(normals))[0]
+    return mesh(depth, k_matrix, labels=labels, colors=colors, normals=normals, **mesh_kwargs)
 
 
 # ---- PLY -------------------------------------------------------------------------------------------------------------------------
@@ -248,16 +283,22 @@ def reconstruct_results(results, k_matrix, frames=None, **mesh_kwargs):
 _FORMATS = {True: "binary_little_endian", False: "ascii"}
 
 
-def _vertex_dtype(with_colors):
-    return np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + ([("red", "u1"), ("green", "u1"), ("blue", "u1")] if with_colors else []) + [("label", "<i4")])
+def _vertex_dtype(with_colors, with_normals=False):
+    return np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + ([("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")] if with_normals else []) +
+                    ([("red", "u1"), ("green", "u1"), ("blue", "u1")] if with_colors else []) + [("label", "<i4")])
 
 
 _FACE_DTYPE = np.dtype([("n", "u1"), ("ids", "<i4", (3,))])
 
 
-def _header(binary, comments, nv, with_colors, nf):
+_NORMAL_LINES = ["property float nx", "property float ny", "property float nz"]
+
+
+def _header(binary, comments, nv, with_colors, nf, with_normals=False):
     lines = ["ply", "format %s 1.0" % _FORMATS[bool(binary)]] + ["comment " + c for c in comments] + ["element vertex %d" % nv]
     lines += ["property float x", "property float y", "property float z"]
+    if with_normals:
+        lines += _NORMAL_LINES
     if with_colors:
         lines += ["property uchar red", "property uchar green", "property uchar blue"]
     lines += ["property int label"]
@@ -270,23 +311,28 @@ def write_ply(path, image_dict, binary=True, comment=None):
     """Writes one image's mesh (an entry of Mesh.cpu(): "vertices" [Nv,3] float32, "labels" [Nv] int32, "colors" [Nv,3] uint8 or None,
     "faces" [Nf,3] int32 or None) as a PLY file: binary little-endian or ascii (floats with nine significant digits: they read back
     exactly).  comment: a string or a list of strings, one `comment` line each.  Colour properties and the face element are written only
-    where the dict has them."""
+    where the dict has them, and `property float nx|ny|nz` directly after z where it has "normals" [Nv,3] float32 (Mesh.cpu() of a mesh with
+    normals); a dict without them gives the file it always gave."""
     vertices = np.ascontiguousarray(image_dict["vertices"], dtype=np.float32).reshape(-1, 3)
     nv = vertices.shape[0]
     labels = np.asarray(image_dict["labels"], dtype=np.int32).reshape(-1)
     colors = None if image_dict.get("colors") is None else np.asarray(image_dict["colors"], dtype=np.uint8).reshape(-1, 3)
     faces = None if image_dict.get("faces") is None else np.asarray(image_dict["faces"], dtype=np.int32).reshape(-1, 3)
-    if labels.shape[0] != nv or (colors is not None and colors.shape[0] != nv):
-        raise ValueError("write_ply: %d vertices, %d labels, %s colours" % (nv, labels.shape[0], "no" if colors is None else colors.shape[0]))
+    normals = None if image_dict.get("normals") is None else np.ascontiguousarray(image_dict["normals"], dtype=np.float32).reshape(-1, 3)
+    if labels.shape[0] != nv or (colors is not None and colors.shape[0] != nv) or (normals is not None and normals.shape[0] != nv):
+        raise ValueError("write_ply: %d vertices, %d labels, %s colours, %s normals" % (nv, labels.shape[0], "no" if colors is None else colors.shape[0],
+                                                                                      "no" if normals is None else normals.shape[0]))
     comments = [] if comment is None else ([comment] if isinstance(comment, str) else list(comment))
     if any("\n" in c or "\r" in c for c in comments):
         raise ValueError("write_ply: a comment must be one line")
-    head = _header(binary, comments, nv, colors is not None, None if faces is None else faces.shape[0]).encode("ascii")
+    head = _header(binary, comments, nv, colors is not None, None if faces is None else faces.shape[0], normals is not None).encode("ascii")
     with open(path, "wb") as f:
         f.write(head)
         if binary:
-            rec = np.empty(nv, _vertex_dtype(colors is not None))
+            rec = np.empty(nv, _vertex_dtype(colors is not None, normals is not None))
             rec["x"], rec["y"], rec["z"], rec["label"] = vertices[:, 0], vertices[:, 1], vertices[:, 2], labels
+            if normals is not None:
+                rec["nx"], rec["ny"], rec["nz"] = normals[:, 0], normals[:, 1], normals[:, 2]
             if colors is not None:
                 rec["red"], rec["green"], rec["blue"] = colors[:, 0], colors[:, 1], colors[:, 2]
             f.write(rec.tobytes())
@@ -298,6 +344,8 @@ def write_ply(path, image_dict, binary=True, comment=None):
             rows = []
             for i in range(nv):
                 row = "%.9g %.9g %.9g" % tuple(float(x) for x in vertices[i])
+                if normals is not None:
+                    row += " %.9g %.9g %.9g" % tuple(float(x) for x in normals[i])
                 if colors is not None:
                     row += " %d %d %d" % tuple(int(x) for x in colors[i])
                 rows.append(row + " %d" % int(labels[i]))
@@ -312,7 +360,8 @@ def _bad(path, why):
 
 def read_ply(path):
     """Reads back exactly the files write_ply makes (anything else: ValueError) -> the dict write_ply took ("vertices", "faces", "labels",
-    "colors"; faces / colors None where the file has none) plus "comments": the list of comment strings."""
+    "colors"; faces / colors None where the file has none; "normals" only where the file has them) plus "comments": the list of comment
+    strings."""
     with open(path, "rb") as f:
         data = f.read()
     end = data.find(b"end_header\n")
@@ -337,20 +386,23 @@ def read_ply(path):
         return int(line[len(prefix):])
     nv = count(lines[i], "element vertex ")
     rest = lines[i + 1:]
-    with_colors = rest[3:6] == ["property uchar red", "property uchar green", "property uchar blue"]
+    with_normals = rest[3:6] == _NORMAL_LINES
+    o = 6 if with_normals else 3                                    # cells of a vertex before its colours
+    with_colors = rest[o:o + 3] == ["property uchar red", "property uchar green", "property uchar blue"]
     nf = None
-    tail = rest[(7 if with_colors else 4):]
+    tail = rest[o + (4 if with_colors else 1):]
     if len(tail) == 3:
         nf = count(tail[0], "element face ")
-    if "".join(l + "\n" for l in lines) != _header(binary, comments, nv, with_colors, nf):
+    if "".join(l + "\n" for l in lines) != _header(binary, comments, nv, with_colors, nf, with_normals):
         raise _bad(path, "the header differs from the one write_ply writes")
-    vdt = _vertex_dtype(with_colors)
+    vdt = _vertex_dtype(with_colors, with_normals)
     if binary:
         need = nv * vdt.itemsize + (0 if nf is None else nf * _FACE_DTYPE.itemsize)
         if len(body) != need:
             raise _bad(path, "%d bytes after the header, %d expected" % (len(body), need))
         rec = np.frombuffer(body, vdt, nv)
         vertices = np.stack([rec["x"], rec["y"], rec["z"]], 1).astype(np.float32) if nv else np.zeros((0, 3), np.float32)
+        normals = (np.stack([rec["nx"], rec["ny"], rec["nz"]], 1).astype(np.float32) if nv else np.zeros((0, 3), np.float32)) if with_normals else None
         labels = rec["label"].astype(np.int32)
         colors = np.stack([rec["red"], rec["green"], rec["blue"]], 1).astype(np.uint8) if with_colors else None
         faces = None
@@ -366,14 +418,15 @@ def read_ply(path):
             raise _bad(path, "the body is not ascii")
         if rows[-1] != "" or len(rows) - 1 != nv + (nf or 0):
             raise _bad(path, "%d complete lines after the header, %d expected" % (len(rows) - 1, nv + (nf or 0)))
-        width = 7 if with_colors else 4
+        width = o + (4 if with_colors else 1)
         try:
             cells = [r.split(" ") for r in rows[:-1]]
             if any(len(c) != width for c in cells[:nv]) or any(len(c) != 4 or c[0] != "3" for c in cells[nv:]):
                 raise ValueError
             vertices = np.array([[float(x) for x in c[:3]] for c in cells[:nv]], dtype=np.float64).reshape(-1, 3).astype(np.float32)
+            normals = np.array([[float(x) for x in c[3:6]] for c in cells[:nv]], dtype=np.float64).reshape(-1, 3).astype(np.float32) if with_normals else None
             labels = np.array([int(c[-1]) for c in cells[:nv]], dtype=np.int64)
-            colors = np.array([[int(x) for x in c[3:6]] for c in cells[:nv]], dtype=np.int64).reshape(-1, 3) if with_colors else None
+            colors = np.array([[int(x) for x in c[o:o + 3]] for c in cells[:nv]], dtype=np.int64).reshape(-1, 3) if with_colors else None
             faces = np.array([[int(x) for x in c[1:]] for c in cells[nv:]], dtype=np.int64).reshape(-1, 3) if nf is not None else None
         except ValueError:
             raise _bad(path, "a malformed line in the body")
@@ -384,4 +437,7 @@ def read_ply(path):
         faces = None if faces is None else faces.astype(np.int32)
     if faces is not None and faces.size and (faces.min() < 0 or faces.max() >= nv):
         raise _bad(path, "a face refers to a vertex the file does not hold")
-    return {"vertices": vertices, "faces": faces, "labels": labels, "colors": colors, "comments": comments}
+    out = {"vertices": vertices, "faces": faces, "labels": labels, "colors": colors, "comments": comments}
+    if with_normals:
+        out["normals"] = normals
+    return out

@@ -23,6 +23,11 @@ two flags only.
 per pixel with a usable depth, the triangles of neighbouring pixels of one plane within --ply_gap of each other in depth): with the iBims-1
 exporters `out/<name>_mesh.ply` from the depth that exporter writes, the file's RGB and the owner map of the masks; with --image
 `<output>_mesh.ply`, which needs the camera as --intrinsics fx,fy,cx,cy.
+
+`--normals` (not in the reference; default off) also writes the surface normals of the depth that run writes as a picture beside the depth
+picture, `<name>_normals.png` (planerecnet_amd.normals: BGR bytes of (z, y, x) * 0.5 + 0.5, black where a pixel has no normal): tangents from
+the neighbours --normals_step pixels away that lie within --normals_gap (a fraction of the smaller depth) and, where there are masks, inside
+the same plane.  With --image it needs --intrinsics.  `--ply_normals` adds the same normals to --ply's file as `nx ny nz`.
 """
 import argparse
 import os
@@ -79,6 +84,13 @@ def parse_args(argv=None):
     p.add_argument("--ply_absolute", action="store_true", help="--ply: --ply_gap is in metres")
     p.add_argument("--ply_planar_only", action="store_true", help="--ply: only pixels a detected plane owns become vertices")
     p.add_argument("--intrinsics", default=None, type=str, help="fx,fy,cx,cy of the --image file in pixels of that file (--ply)")
+    p.add_argument("--normals", action="store_true",
+                   help="also write the surface normals of the depth as a picture (planerecnet_amd.normals): out/<name>_normals.png with --ibims1 / --ibims1_pd, "
+                        "<output>_normals.png with --image (which then needs --intrinsics)")
+    p.add_argument("--normals_step", default=1, type=int, help="--normals / --ply_normals: the distance in pixels of the neighbours a tangent is taken from")
+    p.add_argument("--normals_gap", default=0.05, type=float,
+                   help="--normals / --ply_normals: the largest depth spread of a pixel and a neighbour it uses, as a fraction of the smaller depth")
+    p.add_argument("--ply_normals", action="store_true", help="--ply: the vertices carry their pixels' normals (nx ny nz)")
     global args
     args = p.parse_args(argv)
     if args.contours and args.render != "device":
@@ -102,12 +114,42 @@ def parse_args(argv=None):
             p.error("--ply with --image needs --intrinsics fx,fy,cx,cy: a single image carries no camera")
         if not (args.ply_gap >= 0 and args.ply_gap < float("inf")):
             p.error("--ply_gap must be finite and >= 0")
+    if args.ply_normals and not args.ply:
+        p.error("--ply_normals goes with --ply")
+    if args.normals or args.ply_normals:
+        if args.normals and args.ibims1 is None and args.ibims1_pd is None and args.image is None:
+            p.error("--normals goes with --ibims1, --ibims1_pd or --image")
+        if args.normals and args.image is not None and args.intrinsics is None:
+            p.error("--normals with --image needs --intrinsics fx,fy,cx,cy: a single image carries no camera")
+        if args.normals_step < 1 or not (args.normals_gap >= 0 and args.normals_gap < float("inf")):
+            p.error("--normals_step must be >= 1, --normals_gap finite and >= 0")
     return args
 
 
 def mesh_options():
     """the reconstruct.mesh keywords the --ply flags ask for"""
     return {"max_gap": args.ply_gap, "relative": not args.ply_absolute, "planar_only": args.ply_planar_only}
+
+
+def normal_options():
+    """the normals.from_depth keywords the --normals flags ask for"""
+    return {"step": args.normals_step, "max_gap": args.normals_gap}
+
+
+def ibims1_normals_path(out_folder, name):
+    """<name>_normals.png in out_folder"""
+    return os.path.join(out_folder, name + "_normals.png")
+
+
+def write_normals(path, result, k_matrix):
+    """--normals: one result dict (its "pred_plane_depth" if present, else "pred_depth"; labels = the owner map of its masks) -> the normal
+    picture, made on the device: one uint8 image comes back.  -> (normals [H,W,3], valid [H,W]) on the device"""
+    from planerecnet_amd import normals
+    from planerecnet_amd.reconstruct import results_depth_labels
+    depth, labels = results_depth_labels([result])
+    n, valid, image = normals.from_depth(depth, k_matrix, labels=labels, image=True, **normal_options())
+    _imwrite_bgr(path, image[0].cpu().numpy())
+    return n[0], valid[0]
 
 
 def ibims1_mesh_path(out_folder, name):
@@ -119,7 +161,8 @@ def write_mesh(path, result, k_matrix, rgb, comment=None):
     """--ply: one result dict (its "pred_plane_depth" if present, else "pred_depth"; labels = the owner map of its masks) -> a PLY file;
     rgb: uint8 [H,W,3] array or tensor in the order the file shall hold"""
     from planerecnet_amd.reconstruct import reconstruct_results, write_ply
-    m = reconstruct_results([result], k_matrix, frames=[torch.as_tensor(rgb)], **mesh_options())
+    m = reconstruct_results([result], k_matrix, frames=[torch.as_tensor(rgb)], normals=normal_options() if getattr(args, "ply_normals", False) else None,
+                            **mesh_options())
     write_ply(path, m.cpu()[0], binary=True, comment=comment)
 
 
@@ -229,7 +272,7 @@ def inference_image(net, path, save_path=None, depth_mode="colored"):
     name, ext = os.path.splitext(path if save_path is None else save_path)
     save_path = name + "_seg" + ext if save_path is None else save_path
     depth_path = name + "_dep.png"
-    if args.ply:
+    if args.ply or getattr(args, "normals", False):
         # the depth lives on the resized (and zero-padded) frame: the mesh is cut to the resized picture, the intrinsics follow the resize
         # (pixel centres: x' = (x + 0.5) s - 0.5), the colours are that picture's
         Wr, Hr = calc_size_preserve_ar(W, H, cfg.max_size)
@@ -240,8 +283,11 @@ def inference_image(net, path, save_path=None, depth_mode="colored"):
         r["pred_depth"] = r["pred_depth"][..., :Hr, :Wr]
         if r.get("pred_masks") is not None:
             r["pred_masks"] = r["pred_masks"][:, :Hr, :Wr]
-        rgb = frame[:Hr, :Wr].flip(-1).round().clamp(0, 255).to(torch.uint8)
-        write_mesh(os.path.splitext(save_path)[0] + "_mesh.ply", r, k_matrix, rgb, comment="PlaneRecNet " + os.path.basename(path))
+        if args.ply:
+            rgb = frame[:Hr, :Wr].flip(-1).round().clamp(0, 255).to(torch.uint8)
+            write_mesh(os.path.splitext(save_path)[0] + "_mesh.ply", r, k_matrix, rgb, comment="PlaneRecNet " + os.path.basename(path))
+        if getattr(args, "normals", False):
+            write_normals(name + "_normals.png", r, k_matrix)
     if args.render == "device":
         blended, depth_image = display_on_device(results[0], frame, depth_mode=depth_mode, depth_shift=args.depth_shift, no_mask=args.no_mask,
                                                  no_box=args.no_box, no_text=args.no_text, contours=args.contours)
@@ -321,10 +367,13 @@ def _ibims1_export(net, in_folder, out_folder, planar):
             depth = planar_out["pred_plane_depth"]
         else:
             depth = r["pred_depth"]
-        if args.ply:
+        if args.ply or getattr(args, "normals", False):
             shown = dict(r)
             if planar:
                 shown.update({k: v for k, v in planar_out.items() if k in ("pred_plane_depth", "pred_plane_masks")})
+        if getattr(args, "normals", False):
+            write_normals(ibims1_normals_path(out_folder, name), shown, k_matrix)
+        if args.ply:
             write_mesh(ibims1_mesh_path(out_folder, name), shown, k_matrix, rgb, comment="PlaneRecNet " + os.path.basename(path))
         depth = depth.squeeze().float().cpu().numpy()
         out, preview = ibims1_outputs(out_folder, name)
